@@ -3,6 +3,7 @@
 features, fp32, synthetic MSLR-WEB30K-shaped data resident in HBM (BASELINE.json configs[1]).
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+  python bench.py ... --dump-outputs DIR                  (also writes the last timed step's loss / gradients / parameters)
 
 A step = one optimizer step of the query-sharded trainer on `--batch` slates per GPU: ONE fused launch
 (scorer fwd -> approxNDCG -> scorer bwd -> weight gradients), a fixed-order gradient reduce, one all-reduce
@@ -181,8 +182,8 @@ def secondary_lines(a):
         enc = os.path.join(ROOT, "tools", "bench_encoder.py")
         j = None
         for extra in (["--graph"], []):          # the whole step as one hipGraph (device-side dropout epoch); eager launches if capture fails
-            r = subprocess.run([sys.executable, enc, "--batch", "256", "--steps", "10", "--warmup", "3"] + extra, capture_output=True,
-                               text=True, timeout=600)
+            r = subprocess.run([sys.executable, enc, "--batch", "256", "--steps", str(a.steps), "--warmup", str(a.warmup)] + extra,
+                               capture_output=True, text=True, timeout=600)
             lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             if lines:
                 j = json.loads(lines[-1])
@@ -195,6 +196,20 @@ def secondary_lines(a):
     except Exception as e:
         out["config5"] = {"error": f"{type(e).__name__}: {e}"[:200]}
     return out
+
+
+def dump_outputs(out_dir, loss, net):
+    """What the last timed step handed its caller, as DIR/<name>.npy (fp32): the global loss trainer.step returned, every
+    parameter's gradient (p.grad, a view of the flat [grads | loss] buffer the step filled) and every parameter as the
+    optimizer left it.  Inputs, weights and dropout seeds are fixed by the arguments, so two builds can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    for name, p in net.named_parameters():
+        arrays[f"grad.{name}"] = p.grad
+        arrays[f"param.{name}"] = p
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def main():
@@ -213,7 +228,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the secondary measurements attached to the default headline line (split-precision variant, 136-64-1 net)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the loss, gradients and parameters of the last step as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -303,6 +322,8 @@ def main():
         # so the roofline figures are taken over the whole step instead of over one kernel
         kern_ms = dt / a.steps * 1e3
     final_loss = float(loss)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, loss, net)
 
     if rank == 0:
         slates_per_s = world * B * a.steps / dt
