@@ -106,27 +106,42 @@ int ltr_enc_drop_cast_colsum(const float *dx, int64_t T, int N, float p, uint64_
 /* ---- attention(query, key, value, mask, dropout), transformer.py:145-164, for all heads of all slates.
  *   qkv [T][3*d] bf16 (d = h*dk; Q | K | V, head hd at columns hd*dk ..), mask [B][S] uint8 (1 = padded document:
  *   masked_fill(mask == 1, -inf), :158-159; NULL = no padding), ctx [T][d] bf16 (heads concatenated, :207-209).
- *   Whole-row softmax in registers (no online rescaling), S <= 512, dk <= 32.  A slate whose documents are all
+ *   1 <= S <= 2048, dk <= 32, h * dk % 8 == 0.  S <= 512: one workgroup per (slate, head), whole-row softmax in registers (no
+ *   online rescaling).  S > 512: the key-tiled kernels of ltr_enc_attention_fwd_tiled below.  A slate whose documents are all
  *   masked yields zeros (the reference yields NaN). */
 int ltr_enc_attention_fwd(const uint16_t *qkv, const uint8_t *mask, int B, int S, int h, int dk, float drop_p,
                           uint64_t seed, int stream_id, uint16_t *ctx, void *stream);
 /* dqkv [T][3*d] bf16 from dctx [T][d] bf16 and the forward's output ctx [T][d] (row sums dP . P = dctx . ctx per head);
- * probabilities are recomputed. */
+ * probabilities are recomputed.  S <= 512 only: above that the backward needs the forward's row statistics
+ * (ltr_enc_attention_bwd_lse), and this entry returns LTR_ERR_SHAPE. */
 int ltr_enc_attention_bwd(const uint16_t *qkv, const uint16_t *ctx, const uint16_t *dctx, const uint8_t *mask, int B, int S, int h,
                           int dk, float drop_p, uint64_t seed, int stream_id, uint16_t *dqkv, void *stream);
 
 /* The same pair with the row statistic kept between them: lse [B*h][S] fp32 = log2 sum_k 2^(log2(e) s_qk / sqrt(dk)) over the
  * unmasked keys (+inf for a query without one), written by the forward (NULL = not wanted) and read by the backward, which
  * then evaluates every probability ONCE, key-major (dk <= 16 and S <= 256; otherwise, or with lse == NULL, the two-phase
- * kernel of ltr_enc_attention_bwd runs).  This is what the training step uses. */
+ * kernel of ltr_enc_attention_bwd runs).  This is what the training step uses.  S > 512: the key-tiled pair below (the backward
+ * then requires lse, else LTR_ERR_SHAPE). */
 int ltr_enc_attention_fwd_lse(const uint16_t *qkv, const uint8_t *mask, int B, int S, int h, int dk, float drop_p,
                               uint64_t seed, int stream_id, uint16_t *ctx, float *lse, void *stream);
 int ltr_enc_attention_bwd_lse(const uint16_t *qkv, const uint16_t *ctx, const uint16_t *dctx, const float *lse, const uint8_t *mask,
                               int B, int S, int h, int dk, float drop_p, uint64_t seed, int stream_id, uint16_t *dqkv, void *stream);
 
+/* The key-tiled pair at any 1 <= S <= 2048 (what the two entries above run for S > 512; explicit here so they can be compared with
+ * the whole-row kernels where both apply).  lse is required (LTR_ERR_NULL otherwise); same lse, dropout stream and outputs.
+ *   forward:  one workgroup per (slate, head, 64-query block); 64-key tiles staged in LDS; online softmax (running max and sum,
+ *             O rescaled when the max grows); dropout on the unnormalised probabilities, O divided by the sum at the end.
+ *   backward: dK / dV per (slate, head, 64-key block) walking 64-query tiles, then dQ per (slate, head, 64-query block) walking
+ *             64-key tiles; both recompute p = 2^(log2(e) s / sqrt(dk) - lse).  Deterministic: no atomics, no scratch. */
+int ltr_enc_attention_fwd_tiled(const uint16_t *qkv, const uint8_t *mask, int B, int S, int h, int dk, float drop_p,
+                                uint64_t seed, int stream_id, uint16_t *ctx, float *lse, void *stream);
+int ltr_enc_attention_bwd_tiled(const uint16_t *qkv, const uint16_t *ctx, const uint16_t *dctx, const float *lse, const uint8_t *mask,
+                                int B, int S, int h, int dk, float drop_p, uint64_t seed, int stream_id, uint16_t *dqkv, void *stream);
+
 /* p_attn, the second value `attention()` returns (transformer.py:161-164; MultiHeadedAttention keeps it in `.attn`, :207):
  * probs [B][h][S][S] fp32 = dropout(softmax(q k^T / sqrt(dk) masked)), from the same bf16 q, k and the same dropout stream
- * as ltr_enc_attention_fwd.  Forward-only helper for callers that inspect the attention map; not on the training path. */
+ * as ltr_enc_attention_fwd.  Forward-only helper for callers that inspect the attention map; not on the training path.
+ * 1 <= S <= 2048 (above 512: 2^(log2(e) s / sqrt(dk) - lse) with lse from an online pass over the keys). */
 int ltr_enc_attention_probs(const uint16_t *qkv, const uint8_t *mask, int B, int S, int h, int dk, float drop_p, uint64_t seed,
                             int stream_id, float *probs, void *stream);
 

@@ -10,7 +10,8 @@
 //   * attention: one workgroup per (slate, head); the whole S x S score row block of a 16-query tile lives in a
 //     wave's registers (S^T = K Q^T orientation: the softmax axis is register-local + two lane swaps), P^T feeds the
 //     P V product as the B operand straight from those registers.  The backward recomputes P in both orientations
-//     (query-major for dQ, key-major for dK / dV) instead of transposing through LDS.
+//     (query-major for dQ, key-major for dK / dV) instead of transposing through LDS.  Slates of 513..2048 documents take the
+//     key-tiled online-softmax kernels of ltr_attention_tiled.h.
 //   * LayerNorm / output scoring: one wave per token, fp32 statistics; parameter gradients as fixed-order
 //     per-workgroup partials (no float atomics anywhere).
 #include "../../include/ltr_encoder.h"
@@ -1981,6 +1982,8 @@ __global__ void __launch_bounds__(256) attn_probs_kernel(AttArgs a, float *__res
     }
 }
 
+#include "ltr_attention_tiled.h"     // S = 513 .. 2048 (and the explicit _tiled entries)
+
 // one instantiation (and one set of per-device attribute flags) per kernel variant
 template <int KTMAX, bool FULL, bool BWD>
 int launch_att_tagged(const AttArgs &a, size_t lds, hipStream_t stream) {
@@ -2025,9 +2028,9 @@ int dispatch_att(const AttArgs &a, size_t lds, hipStream_t stream) {
     return Sp == 512 ? launch_att_tagged<32, true, BWD>(a, lds, stream) : launch_att_tagged<32, false, BWD>(a, lds, stream);
 }
 
-int check_att(const uint16_t *qkv, const void *other, int B, int S, int h, int dk, float p) {
+int check_att(const uint16_t *qkv, const void *other, int B, int S, int h, int dk, float p, int smax = 512) {
     if (!qkv || !other) return LTR_ERR_NULL;
-    if (B < 0 || S < 1 || S > 512 || h < 1 || dk < 1 || dk > kDkPad) return LTR_ERR_SHAPE;
+    if (B < 0 || S < 1 || S > smax || h < 1 || dk < 1 || dk > kDkPad) return LTR_ERR_SHAPE;
     if ((h * dk) % 8 != 0) return LTR_ERR_SHAPE;
     if (!(p >= 0.f) || p >= 1.f) return LTR_ERR_PARAM;
     if (((uintptr_t)qkv & 15u) || ((uintptr_t)other & 15u)) return LTR_ERR_ALIGN;
@@ -2230,9 +2233,10 @@ int ltr_enc_drop_cast_colsum(const float *dx, int64_t T, int N, float p, uint64_
 
 int ltr_enc_attention_fwd_lse(const uint16_t *qkv, const uint8_t *mask, int B, int S, int h, int dk, float drop_p,
                               uint64_t seed, int stream_id, uint16_t *ctx, float *lse, void *stream) {
-    if (int rc = check_att(qkv, ctx, B, S, h, dk, drop_p)) return rc;
+    if (int rc = check_att(qkv, ctx, B, S, h, dk, drop_p, kTiledMaxS)) return rc;
     if (B == 0) return LTR_OK;
     AttArgs a{qkv, nullptr, nullptr, mask, ctx, B, S, h, dk, drop_p, (unsigned long long)seed, stream_id, lse};
+    if (S > 512) return launch_att_tiled_fwd(a, (hipStream_t)stream);
     return dispatch_att<false>(a, att_fwd_lds(S), (hipStream_t)stream);
 }
 int ltr_enc_attention_fwd(const uint16_t *qkv, const uint8_t *mask, int B, int S, int h, int dk, float drop_p,
@@ -2243,10 +2247,12 @@ int ltr_enc_attention_fwd(const uint16_t *qkv, const uint8_t *mask, int B, int S
 int ltr_enc_attention_bwd_lse(const uint16_t *qkv, const uint16_t *ctx, const uint16_t *dctx, const float *lse, const uint8_t *mask,
                               int B, int S, int h, int dk, float drop_p, uint64_t seed, int stream_id, uint16_t *dqkv, void *stream) {
     if (!dctx || !ctx) return LTR_ERR_NULL;
-    if (int rc = check_att(qkv, dqkv, B, S, h, dk, drop_p)) return rc;
+    // above 512 only the tiled backward exists, and it needs the forward's row statistics
+    if (int rc = check_att(qkv, dqkv, B, S, h, dk, drop_p, lse ? kTiledMaxS : 512)) return rc;
     if (((uintptr_t)dctx & 15u) || ((uintptr_t)ctx & 15u)) return LTR_ERR_ALIGN;
     if (B == 0) return LTR_OK;
     AttArgs a{qkv, dctx, ctx, mask, dqkv, B, S, h, dk, drop_p, (unsigned long long)seed, stream_id, const_cast<float *>(lse)};
+    if (S > 512) return launch_att_tiled_bwd(a, (hipStream_t)stream);
     if (att_km_ok(a)) return dispatch_att_km(a, (hipStream_t)stream);
     return dispatch_att<true>(a, att_bwd_lds(S), (hipStream_t)stream);
 }
@@ -2255,11 +2261,30 @@ int ltr_enc_attention_bwd(const uint16_t *qkv, const uint16_t *ctx, const uint16
     return ltr_enc_attention_bwd_lse(qkv, ctx, dctx, nullptr, mask, B, S, h, dk, drop_p, seed, stream_id, dqkv, stream);
 }
 
+int ltr_enc_attention_fwd_tiled(const uint16_t *qkv, const uint8_t *mask, int B, int S, int h, int dk, float drop_p,
+                                uint64_t seed, int stream_id, uint16_t *ctx, float *lse, void *stream) {
+    if (!lse) return LTR_ERR_NULL;
+    if (int rc = check_att(qkv, ctx, B, S, h, dk, drop_p, kTiledMaxS)) return rc;
+    if (B == 0) return LTR_OK;
+    AttArgs a{qkv, nullptr, nullptr, mask, ctx, B, S, h, dk, drop_p, (unsigned long long)seed, stream_id, lse};
+    return launch_att_tiled_fwd(a, (hipStream_t)stream);
+}
+int ltr_enc_attention_bwd_tiled(const uint16_t *qkv, const uint16_t *ctx, const uint16_t *dctx, const float *lse, const uint8_t *mask,
+                                int B, int S, int h, int dk, float drop_p, uint64_t seed, int stream_id, uint16_t *dqkv, void *stream) {
+    if (!dctx || !ctx || !lse) return LTR_ERR_NULL;
+    if (int rc = check_att(qkv, dqkv, B, S, h, dk, drop_p, kTiledMaxS)) return rc;
+    if (((uintptr_t)dctx & 15u) || ((uintptr_t)ctx & 15u)) return LTR_ERR_ALIGN;
+    if (B == 0) return LTR_OK;
+    AttArgs a{qkv, dctx, ctx, mask, dqkv, B, S, h, dk, drop_p, (unsigned long long)seed, stream_id, const_cast<float *>(lse)};
+    return launch_att_tiled_bwd(a, (hipStream_t)stream);
+}
+
 int ltr_enc_attention_probs(const uint16_t *qkv, const uint8_t *mask, int B, int S, int h, int dk, float drop_p, uint64_t seed,
                             int stream_id, float *probs, void *stream) {
-    if (int rc = check_att(qkv, probs, B, S, h, dk, drop_p)) return rc;
+    if (int rc = check_att(qkv, probs, B, S, h, dk, drop_p, kTiledMaxS)) return rc;
     if (B == 0) return LTR_OK;
     AttArgs a{qkv, nullptr, nullptr, mask, nullptr, B, S, h, dk, drop_p, (unsigned long long)seed, stream_id, nullptr};
+    if (S > 512) return launch_att_probs_tiled(a, probs, (hipStream_t)stream);
     const long long rows = (long long)B * h * S;
     hipLaunchKernelGGL(attn_probs_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a, probs);
     return status();

@@ -300,6 +300,9 @@ LN_EPS = 1e-6          # transformer.py:69
 STD_LN_EPS = 1e-5      # nn.LayerNorm default (multiLayer.py:27)
 
 
+MAX_ATTN_SLATE = 2048   # include/ltr_encoder.h: whole-row attention kernels up to 512, key-tiled ones above
+
+
 def _run_forward(spec, x, mask, seed, training, params):
     """FCModel + encoder blocks.  Returns everything the scoring tail and the backward need."""
     require_device(x, *params)
@@ -308,8 +311,8 @@ def _run_forward(spec, x, mask, seed, training, params):
     B, S, F = x.shape
     T = B * S
     dev = x.device
-    if spec.has_encoder and S > 512:
-        raise ValueError("the attention kernels hold a whole slate: slate_length <= 512")
+    if spec.has_encoder and S > MAX_ATTN_SLATE:
+        raise ValueError(f"the attention kernels take slates of at most {MAX_ATTN_SLATE} documents: slate_length <= {MAX_ATTN_SLATE}")
     if spec.has_encoder and mask is None:
         raise AttributeError("'NoneType' object has no attribute 'unsqueeze'")      # transformer.py:55
     p_fc = spec.fc_dropout if training else 0.0
