@@ -307,6 +307,46 @@ int ltr_fused_step_lambda(int net, const float *X, const float *labels, int B, i
                           float *slate_count, float *partials, int grid, void *stream);
 
 /* =====================================================================================================
+ * FC-only make_model rankers (csrc/ltr_linear.hip): LTRModel = FCModel -> OutputLayer with no transformer, d_output = 1 and no
+ * active dropout.  FCModel (architeture/multiLayer.py:13-51) and OutputLayer (:94-124) hard-wire nn.Identity activations, so the
+ * network make_model builds (:127-149) is ONE affine map of h_0 (x, or LayerNorm(x) with input_norm):
+ *   v_L = w_o, v_{i-1} = v_i W_i, w_eff = v_0, b_eff = b_o + sum_i v_i . b_i.
+ * One training step: ltr_linear_fold -> (ltr_linear_fused_step | ltr_linear_scores + loss kernel + ltr_linear_grad_partials)
+ * -> ltr_linear_unfold_grads.  Exact fp32 on the documents, fp64 in the fold / unfold chains; no atomics.
+ *
+ * `params` (HOST array of device pointers) in LTRModel._ltr_params() order: [gamma, beta] if input_norm, then W_1 [n_1][F], b_1, ...,
+ * W_L [n_L][n_{L-1}], b_L, then w_o [1][n_L], b_o [1].  sizes[i] = n_{i+1} (host, n_layers entries; n_layers = 0: OutputLayer
+ * only).  ws: ltr_linear_ws_doubles() fp64, device, shared by the fold and the unfold of one step. */
+#define LTR_LINEAR_MAX_LAYERS 16
+int64_t ltr_linear_ws_doubles(int n_layers, int F, const int *sizes);     /* < 0: shape rejected */
+/* weff[F + 2] = [w_eff (o gamma with input_norm) | b_eff (+ w_eff . beta) | sum of the first F]   multiLayer.py:13-51, :94-124 */
+int ltr_linear_fold(int n_layers, int F, const int *sizes, int input_norm, const float *const *params, double *ws, float *weff,
+                    void *stream);
+/* partials [grid][F + 1] = per-workgroup [sum_d ds_d xhat_d | sum_d ds_d] (fixed-order sum here) -> the flat gradient in _ltr_params()
+ * order: H_0 = Ghat (gamma o Ghat + beta G_1), H_i = W_i H_{i-1} + b_i G_1, dW_i = v_i H_{i-1}^T, db_i = v_i G_1, dw_o = H_L,
+ * db_o = G_1, dgamma = w_eff o Ghat, dbeta = w_eff G_1.  ws as left by ltr_linear_fold on the same parameters.   multiLayer.py:127-149 */
+int ltr_linear_unfold_grads(int n_layers, int F, const int *sizes, int input_norm, const float *const *params, const float *partials,
+                            int grid, double *ws, float *flat, void *stream);
+/* scores[n] = weff . x + weff[F] (input_norm: rstd (weff . (x - mean)) + weff[F]; stats[n][2] = (mean, rstd)).  F <= 1024.
+ * multiLayer.py:36-46 + :107-113 on the folded vector. */
+int ltr_linear_scores(const float *X, int64_t n, int F, const float *weff, int input_norm, float *scores, float *stats, void *stream);
+/* partials[g] = [sum_d ds_d xhat_d | sum_d ds_d] over workgroup g's contiguous document range (grid workgroups).  F <= 1024. */
+int ltr_linear_grad_partials(const float *X, int64_t n, int F, const float *dscores, const float *stats, int input_norm, float *partials,
+                             int grid, void *stream);
+/* 1 when the one-launch step takes (F, S): S in {32, 64, 128}, F % 4 == 0, F <= 256. */
+int ltr_linear_fused_supported(int F, int S);
+/* One launch: scores, per-slate loss (loss_kind LTR_LOSS_APPROXNDCG / LTR_LOSS_LISTNET / 2 = lambdaLoss with scheme, k, sigma, mu,
+ * lambda_eps, log_base as in ltr_lambda_fwd_bwd), d loss / d s and the gradient partials [grid][F + 1] of
+ * sum_b grad_scale slate_loss[b].  slate_count (lambdaLoss, may be NULL): kept pairs per slate.  X and weff 16-byte aligned.
+ * main_batch_execution.py:128-170 with net_structure = allrank is the call chain this replaces. */
+int ltr_linear_fused_step(int loss_kind, const float *X, const float *labels, int B, int S, int F, const float *weff, int input_norm,
+                          float alpha, float eps, float pad, int apply_sigmoid, int scheme, int k, float sigma, float mu,
+                          float lambda_eps, int log_base, float grad_scale, float *slate_loss, float *slate_count, float *partials,
+                          int grid, void *stream);
+/* Workgroups of ltr_linear_fused_step / ltr_linear_grad_partials on a device with n_cus compute units (2 per CU). */
+int ltr_linear_grid(int n_cus);
+
+/* =====================================================================================================
  * Data path in front of the pipeline.
  *
  * ---- get_data(info_dataset, type_file)                                        utils/dataset.py:33-69

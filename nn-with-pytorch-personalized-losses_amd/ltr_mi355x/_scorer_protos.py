@@ -23,6 +23,16 @@ PROTOTYPES = {
     "ltr_debug_set_stamps": (c_int, [P, c_int]),
     "ltr_fused_step_lambda": (c_int, [c_int, P, P, c_int, c_int, P, c_int, c_uint64, P, P, c_int, c_int, c_float, c_float,
                                       c_float, c_float, c_int, c_float, P, P, P, c_int, P]),
+    # FC-only make_model rankers (csrc/ltr_linear.hip)
+    "ltr_linear_ws_doubles": (c_int64, [c_int, c_int, P]),
+    "ltr_linear_fold": (c_int, [c_int, c_int, P, c_int, P, P, P, P]),
+    "ltr_linear_unfold_grads": (c_int, [c_int, c_int, P, c_int, P, P, c_int, P, P, P]),
+    "ltr_linear_scores": (c_int, [P, c_int64, c_int, P, c_int, P, P, P]),
+    "ltr_linear_grad_partials": (c_int, [P, c_int64, c_int, P, P, c_int, P, c_int, P]),
+    "ltr_linear_fused_supported": (c_int, [c_int, c_int]),
+    "ltr_linear_fused_step": (c_int, [c_int, P, P, c_int, c_int, c_int, P, c_int, c_float, c_float, c_float, c_int, c_int, c_int,
+                                      c_float, c_float, c_float, c_int, c_float, P, P, P, c_int, P]),
+    "ltr_linear_grid": (c_int, [c_int]),
 }
 
 

@@ -304,7 +304,8 @@ def _dropout_keep_mask_half(seed, layer, n_docs, H, device):
 
 
 class FusedRanker:
-    """One-launch training pass for a DoubleLayerNet / TripleLayerNet with a listwise loss.
+    """One-launch training pass for a DoubleLayerNet / TripleLayerNet -- or an FC-only make_model LTRModel, which runs folded
+    (ltr_mi355x.linear.LinearFusedRanker) -- with a listwise loss.
 
         ranker = FusedRanker(net, loss="approxNDCG")
         loss = ranker.step(X, y)          # X [B,S,F] fp32 device, y [B,S]; fills p.grad for every parameter
@@ -317,6 +318,13 @@ class FusedRanker:
     """
 
     LOSSES = {"approxNDCG": LOSS_APPROXNDCG, "listnet": LOSS_LISTNET, "lambdaLoss": LOSS_LAMBDA}
+
+    def __new__(cls, module, *args, **kwargs):
+        # an FC-only make_model LTRModel (architeture/multiLayer.py) runs folded into one scoring vector: ltr_mi355x.linear
+        if cls is FusedRanker and hasattr(module, "output_layer") and not hasattr(module, "_ltr_net"):
+            from .linear import LinearFusedRanker
+            cls = LinearFusedRanker
+        return super().__new__(cls)
 
     def __init__(self, module, loss="approxNDCG", alpha=1.0, eps=1e-10, padded_value_indicator=-1,
                  apply_sigmoid=False, grid=None, weighing_scheme=None, k=None, sigma=1.0, mu=10.0,
