@@ -81,6 +81,14 @@ class deferred_reductions:
         return False
 
 
+def splitk_epilogue(parts, ks, T, d, bias, p, seed, stream_id, residual, out):
+    """out [T, d] = residual + drop(sum of the ks slices of parts [ks, T, d] + bias) -> ltr_enc_splitk_epilogue: the epilogue of the
+    split-K GEMM-path FFN output; the arithmetic, dropout stream and element indices of gemm()'s own epilogue.  bias / residual may be None."""
+    check(lib().ltr_enc_splitk_epilogue(_ptr(parts), int(ks), int(T), int(d), _ptr(bias), float(p), int(seed) & (2 ** 64 - 1), int(stream_id),
+                                        _ptr(residual), _ptr(out), _stream()), "ltr_enc_splitk_epilogue")
+    return out
+
+
 def sum_partials(parts, nsplit, n, out=None, accumulate=False):
     q = deferred_reductions.current
     if q is not None and out is None and not accumulate:
@@ -381,8 +389,7 @@ def _run_forward(spec, x, mask, seed, training, params):
                 if ks > 1:          # 32 output tiles, 32 k-steps each: split-K partials, then bias + dropout + residual in the reduce
                     parts = torch.empty((ks, T, d), dtype=torch.float32, device=dev)
                     gemm(hid, w216, T, d, dff, Cf=parts, splits=ks)
-                    check(lib().ltr_enc_splitk_epilogue(_ptr(parts), ks, T, d, _ptr(b2), float(p_enc), int(seed) & (2 ** 64 - 1),
-                                                        stream_ffn_out(l), _ptr(x1), _ptr(x2), _stream()), "ltr_enc_splitk_epilogue")
+                    splitk_epilogue(parts, ks, T, d, b2, p_enc, seed, stream_ffn_out(l), x1, x2)
                 else:
                     gemm(hid, w216, T, d, dff, Cf=x2, bias=b2, residual=x1, drop_p=p_enc, seed=seed, drop_stream=stream_ffn_out(l))
             st["layers"].append((x0, n1, qkv, ctxb, x1, n2, hid, lse))

@@ -167,3 +167,28 @@ def test_oracle_reproduces_reference_on_the_benched_config5_network():
         ref = g5.arr(case, "g/" + k) if len(sh) == 1 else g5.arr(case, "grows/" + k)
         got = grads[k].numpy() if len(sh) == 1 else grads[k][:4].numpy()
         assert np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-3 * gmax) <= 5e-4, k
+
+
+# (M, N, K) -> ks that tests/test_encoder_small_step_gpu.py and tests/test_graph_step_gpu.py name as the split-K factor they exercise
+_SMALL_STEP_KS = {(384, 128, 1024): 2, (384, 128, 1536): 3, (384, 128, 2048): 4, (384, 64, 2048): 4, (384, 136, 2048): 4,
+                  (512, 128, 1536): 3, (512, 128, 2048): 4, (1200, 136, 2048): 4, (4096, 128, 2048): 4, (9000, 128, 2048): 3,
+                  (200, 128, 128): 1, (256, 64, 128): 1, (65536, 128, 2048): 1}
+
+
+def test_small_step_split_k_factor():
+    """encoder._small_step_splits, the split-K factor of the GEMM-path FFN's (T, d_model, d_ff) GEMMs: between 1 and 4, and no
+    slice of the kernel's partition (ceil(ksteps / ks) whole 64-wide k-steps per slice, csrc/ltr_encoder.hip gemm_bf16_kernel) is
+    empty, over every small-step shape the network can produce; plus the values the GPU tests rely on."""
+    from ltr_mi355x.encoder import _small_step_splits
+    Ts = sorted(set(range(1, 16385, 37)) | set(range(128, 16385, 128)) | {384, 512, 4096, 8192, 8193, 9000, 16384})
+    dffs = list(range(128, 4097, 128)) + [8, 64, 1000, 1160]
+    for d in (24, 64, 128, 136):
+        for dff in dffs:
+            ksteps = (dff + 63) // 64
+            for T in Ts:
+                ks = _small_step_splits(T, d, dff)
+                assert 1 <= ks <= 4, (T, d, dff, ks)
+                per = (ksteps + ks - 1) // ks
+                assert (ks - 1) * per < ksteps, ("empty slice", T, d, dff, ks)
+    for (M, N, K), ks in _SMALL_STEP_KS.items():
+        assert _small_step_splits(M, N, K) == ks, (M, N, K)

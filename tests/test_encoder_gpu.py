@@ -479,21 +479,117 @@ def _oracle_gate(got, scores, sd, x, mask, cfg, y, keep=None, what="", loss_fn=N
     return out
 
 
-@pytest.mark.parametrize("case", golden("encoder").cases, ids=lambda c: c["id"])
-def test_network_vs_reference_golden(case):
+class FfnCalls:
+    """Counting wrappers around encoder.gemm and encoder.splitk_epilogue for one training step.  The FFN's GEMMs are told apart
+    from the others by their operands: the hidden GEMM writes `hid` (relu, bf16 out), the output GEMM reads it; the gate GEMM
+    writes dz1, the input-gradient GEMM reads it with A row-major (the weight-gradient GEMM reads it k-major).  Every bf16 output is
+    held until reset(), so that no later tensor takes over its address."""
+
+    def __init__(self, monkeypatch, enc):
+        self.enc = enc
+        self.reset()
+        gemm, epilogue = enc.gemm, enc.splitk_epilogue
+
+        def counting_gemm(A, B, M, N, K, **kw):
+            self.gemms.append(dict(A=A.data_ptr(), M=M, N=N, K=K, a_kmajor=bool(kw.get("a_kmajor")), b_kmajor=bool(kw.get("b_kmajor")),
+                                   splits=int(kw.get("splits", 1)), relu=bool(kw.get("relu")), gate=kw.get("gate") is not None,
+                                   Cf=kw.get("Cf") is not None, Cb=None if kw.get("Cb") is None else kw["Cb"].data_ptr(),
+                                   residual=kw.get("residual") is not None, drop_stream=kw.get("drop_stream")))
+            if kw.get("Cb") is not None:
+                self.held.append(kw["Cb"])
+            return gemm(A, B, M, N, K, **kw)
+
+        def counting_epilogue(parts, ks, T, d, bias, p, seed, stream_id, residual, out):
+            self.epilogues.append(dict(ks=ks, T=T, d=d, bias=bias is not None, p=p, stream_id=stream_id, residual=residual is not None))
+            return epilogue(parts, ks, T, d, bias, p, seed, stream_id, residual, out)
+
+        monkeypatch.setattr(enc, "gemm", counting_gemm)
+        monkeypatch.setattr(enc, "splitk_epilogue", counting_epilogue)
+
+    def reset(self):
+        self.gemms, self.epilogues, self.held = [], [], []
+
+    def ffn(self, T, d, dff):
+        hidden = [g for g in self.gemms if g["relu"] and g["Cb"] is not None and (g["M"], g["N"], g["K"]) == (T, dff, d)]
+        hid = {g["Cb"] for g in hidden}
+        dz1 = {g["Cb"] for g in self.gemms if g["gate"] and (g["M"], g["N"], g["K"]) == (T, dff, d)}
+        out = [g for g in self.gemms if g["A"] in hid and not g["a_kmajor"] and not g["b_kmajor"]]
+        dn2 = [g for g in self.gemms if g["A"] in dz1 and not g["a_kmajor"] and g["b_kmajor"]]
+        return hidden, out, dn2
+
+    def assert_gemm_path(self, T, d, dff, n_layers, ks, p):
+        """Per layer: one hidden GEMM, one (T, d, d_ff) output GEMM with ks slices (+ one split-K epilogue when ks > 1, the GEMM's
+        own epilogue otherwise), one (T, d, d_ff) input-gradient GEMM with ks slices."""
+        E = self.enc
+        hidden, out, dn2 = self.ffn(T, d, dff)
+        assert len(hidden) == n_layers, hidden
+        assert [(g["M"], g["N"], g["K"], g["splits"]) for g in out] == [(T, d, dff, ks)] * n_layers, out
+        assert [(g["M"], g["N"], g["K"], g["splits"], g["Cf"], g["Cb"]) for g in dn2] == [(T, d, dff, ks, True, None)] * n_layers, dn2
+        if ks > 1:
+            assert not any(g["residual"] for g in out)
+            assert self.epilogues == [dict(ks=ks, T=T, d=d, bias=True, p=p, stream_id=E.stream_ffn_out(l), residual=True)
+                                      for l in range(n_layers)], self.epilogues
+        else:
+            assert not self.epilogues
+            assert [(g["residual"], g["drop_stream"]) for g in out] == [(True, E.stream_ffn_out(l)) for l in range(n_layers)]
+
+    def assert_fused_path(self, T, d, dff):
+        hidden, out, dn2 = self.ffn(T, d, dff)
+        assert not hidden and not out and not dn2 and not self.epilogues
+
+
+def _select_ffn(monkeypatch, ffn):
+    """ffn "fused": LTR_ENC_FUSED_FFN=1, the fused FFN kernels wherever they exist (what the suite runs); "default": the variable unset,
+    what a real run takes (the GEMM path below FUSED_FFN_MIN_TOKENS tokens per step)."""
+    if ffn == "default":
+        monkeypatch.delenv("LTR_ENC_FUSED_FFN", raising=False)
+    else:
+        monkeypatch.setenv("LTR_ENC_FUSED_FFN", "1")
+
+
+def _assert_ffn_path(calls, ffn, T, d, dff, n_layers, p):
+    """The FFN path the step took, from the counting wrappers: fused where the selection says so, else the GEMMs with the
+    heuristic's split-K factor."""
+    from ltr_mi355x import encoder as E
+    if E.fused_ffn_enabled(d, dff, T):
+        assert ffn == "fused"
+        calls.assert_fused_path(T, d, dff)
+    else:
+        calls.assert_gemm_path(T, d, dff, n_layers, E._small_step_splits(T, d, dff), p)
+
+
+def _golden_ffn_cases():
+    """Every golden under the forced fused FFN (test ids unchanged), and every golden with an encoder on the default path too."""
+    cases = golden("encoder").cases
+    return ([pytest.param(c, "fused", id=c["id"]) for c in cases] +
+            [pytest.param(c, "default", id=c["id"] + "-default_ffn") for c in cases if c["transformer"]])
+
+
+@pytest.mark.parametrize("case,ffn", _golden_ffn_cases())
+def test_network_vs_reference_golden(case, ffn, monkeypatch):
     import ltr_encoder_oracle as EO
     from losses.approxNDCG import approxNDCGLoss
+    from ltr_mi355x import encoder as E
+    _select_ffn(monkeypatch, ffn)
     g = golden("encoder")
     net, sd = _build(case, g)
     net.eval()
     x = torch.from_numpy(g.arr(case, "x")).to(DEV)
     y = torch.from_numpy(g.arr(case, "y")).to(DEV)
     mask = torch.from_numpy(g.arr(case, "mask")).to(DEV) if case["has_mask"] else None
+    tr = case["transformer"]
+    calls = FfnCalls(monkeypatch, E) if tr else None
     scores = net(x, mask, None)
     assert scores.shape == (case["B"], case["S"])
     loss = approxNDCGLoss(scores, y)
     loss.backward()
     got = {k: p.grad.cpu().double() for k, p in net.named_parameters()}
+    if tr:
+        fc_sizes = (case["fc_model"] or {}).get("sizes") or []
+        d, T = fc_sizes[-1] if fc_sizes else case["n_features"], case["B"] * case["S"]
+        if ffn == "default":
+            assert not E.fused_ffn_enabled(d, tr["d_ff"], T)
+        _assert_ffn_path(calls, ffn, T, d, tr["d_ff"], tr["N"], 0.0)
     # (1) the gate: the rounding-faithful oracle at measured-noise bars
     cfg = EO.config_of(dict(fc_model=case["fc_model"], transformer=case["transformer"]), case["n_features"])
     gate = _oracle_gate(got, scores, sd, x, mask, cfg, y, what=case["id"])
@@ -508,22 +604,35 @@ def test_network_vs_reference_golden(case):
     assert cos > 0.99, cos
     loose = max(_gerr(got[k], ref[k], gmax) for k in ref)
     note = "bf16-operand network (BASELINE config 5): bars are the bf16 ones stated in tests/test_encoder_gpu.py, not 1e-5"
-    ledger_record("encoder worst param-grad vs rounding-faithful oracle (max-norm)", gate["max"], noise=gate["noise_max"],
+    tag = f"[{ffn} FFN]"
+    ledger_record(f"encoder {tag} worst param-grad vs rounding-faithful oracle (max-norm)", gate["max"], noise=gate["noise_max"],
                   tol=max(2e-2, 4 * gate["noise_max"]), note=note + f"; min cosine {gate['min_cos']:.6f}")
-    ledger_record("encoder worst param-grad vs rounding-faithful oracle (L2)", gate["l2"], noise=gate["noise_l2"],
+    ledger_record(f"encoder {tag} worst param-grad vs rounding-faithful oracle (L2)", gate["l2"], noise=gate["noise_l2"],
                   tol=max(1.5e-2, 2 * gate["noise_l2"]), note=note)
-    ledger_record("encoder scores vs reference fp32 (ledger only)", relerr(scores.detach().cpu().numpy(), want_s), tol=3e-2, note=note)
-    ledger_record("encoder worst param-grad vs reference fp32 (ledger only, not a gate)", loose, tol=1.0, asserted=False,
+    ledger_record(f"encoder {tag} scores vs reference fp32 (ledger only)", relerr(scores.detach().cpu().numpy(), want_s), tol=3e-2,
+                  note=note)
+    ledger_record(f"encoder {tag} worst param-grad vs reference fp32 (ledger only, not a gate)", loose, tol=1.0, asserted=False,
                   note=note + f"; whole-gradient cosine {cos:.5f}")
 
 
-def test_benched_config5_network_vs_reference_golden():
+def test_benched_config5_network_vs_reference_golden(monkeypatch):
     """The network bench.py / tools/bench_encoder.py time for BASELINE config 5 (FC 136 -> 128, 6 blocks, 8 heads, d_ff 2048,
     slate 256: fused-FFN kernels at 16 chunks, XCD-remapped attention), end to end against the reference."""
+    _config5_vs_reference_golden(monkeypatch, "fused")
+
+
+def test_benched_config5_network_vs_reference_golden_default_ffn(monkeypatch):
+    """The same network and gates on the FFN path a real run takes at the golden's 512 tokens: GEMMs, split-K ks = 4 for the
+    (T, d_model, d_ff) ones, bias + dropout + residual in the split-K epilogue."""
+    _config5_vs_reference_golden(monkeypatch, "default")
+
+
+def _config5_vs_reference_golden(monkeypatch, ffn):
     import copy
     import ltr_encoder_oracle as EO
     from architeture.multiLayer import make_model
     from losses.approxNDCG import approxNDCGLoss
+    _select_ffn(monkeypatch, ffn)
     g = golden("encoder_c5")
     case = g.cases[0]
     net = make_model(fc_model=copy.deepcopy(case["fc_model"]), transformer=copy.deepcopy(case["transformer"]),
@@ -533,13 +642,19 @@ def test_benched_config5_network_vs_reference_golden():
     net.load_state_dict(sd)
     net = net.to(DEV).eval()
     from ltr_mi355x import encoder as enc_mod
-    assert enc_mod.fused_ffn_enabled(128, 2048)
+    T = case["B"] * case["S"]
+    if ffn == "fused":
+        assert enc_mod.fused_ffn_enabled(128, 2048)
+    else:
+        assert not enc_mod.fused_ffn_enabled(128, 2048, T) and enc_mod._small_step_splits(T, 128, 2048) == 4
+    calls = FfnCalls(monkeypatch, enc_mod)
     x, y = torch.from_numpy(g.arr(case, "x")).to(DEV), torch.from_numpy(g.arr(case, "y")).to(DEV)
     mask = torch.from_numpy(g.arr(case, "mask")).to(DEV)
     scores = net(x, mask, None)
     loss = approxNDCGLoss(scores, y)
     loss.backward()
     got = {k: p.grad.cpu().double() for k, p in net.named_parameters()}
+    _assert_ffn_path(calls, ffn, T, 128, 2048, case["transformer"]["N"], 0.0)
     cfg = EO.config_of(dict(fc_model=case["fc_model"], transformer=case["transformer"]), case["n_features"])
     gate = _oracle_gate(got, scores, sd, x, mask, cfg, y, what=case["id"])
     # the reference's own numbers: scores, loss, every vector gradient in full, of every matrix gradient 4 rows + norm + sum
@@ -561,12 +676,14 @@ def test_benched_config5_network_vs_reference_golden():
         worst = max(worst, _gerr(gk, ref, gmax))
     note = "benched config-5 network (3.6 M parameters) vs the reference's fp32 CPU run; bf16 bars (tests/test_encoder_gpu.py)"
     assert worst_norm < 5e-2, worst_norm
-    ledger_record("config-5 network scores vs reference fp32", e_s, tol=3e-2, note=note)
-    ledger_record("config-5 network worst param-grad vs reference fp32 (stored rows; ledger only)", worst, tol=1.0, note=note, asserted=False)
-    ledger_record("config-5 network worst matrix-gradient norm deviation vs reference fp32", worst_norm, tol=5e-2, note=note)
-    ledger_record("config-5 network worst param-grad vs rounding-faithful oracle (max-norm)", gate["max"], noise=gate["noise_max"],
+    tag = f"[{ffn} FFN]"
+    ledger_record(f"config-5 network {tag} scores vs reference fp32", e_s, tol=3e-2, note=note)
+    ledger_record(f"config-5 network {tag} worst param-grad vs reference fp32 (stored rows; ledger only)", worst, tol=1.0, note=note,
+                  asserted=False)
+    ledger_record(f"config-5 network {tag} worst matrix-gradient norm deviation vs reference fp32", worst_norm, tol=5e-2, note=note)
+    ledger_record(f"config-5 network {tag} worst param-grad vs rounding-faithful oracle (max-norm)", gate["max"], noise=gate["noise_max"],
                   tol=max(2e-2, 4 * gate["noise_max"]), note=note + f"; min cosine {gate['min_cos']:.6f}")
-    ledger_record("config-5 network worst param-grad vs rounding-faithful oracle (L2)", gate["l2"], noise=gate["noise_l2"],
+    ledger_record(f"config-5 network {tag} worst param-grad vs rounding-faithful oracle (L2)", gate["l2"], noise=gate["noise_l2"],
                   tol=max(1.5e-2, 2 * gate["noise_l2"]), note=note)
 
 

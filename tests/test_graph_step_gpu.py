@@ -51,15 +51,22 @@ def test_epoch_is_added_to_the_seed(enc):
 
 
 def _net(encoder_cfg, dropout):
+    """encoder_cfg: False (FC only), True (two blocks, d_ff 256) or "small_step" (the README's graphed config-5 step: two blocks,
+    8 heads, d_ff 2048)."""
     from architeture.multiLayer import make_model
     torch.manual_seed(3)
     fc = dict(sizes=[128], input_norm=False, activation=None, dropout=dropout)
-    tr = dict(N=2, d_ff=256, h=4, dropout=dropout, positional_encoding=None) if encoder_cfg else None
+    tr = None
+    if encoder_cfg == "small_step":
+        tr = dict(N=2, d_ff=2048, h=8, dropout=dropout, positional_encoding=None)
+    elif encoder_cfg:
+        tr = dict(N=2, d_ff=256, h=4, dropout=dropout, positional_encoding=None)
     return make_model(fc, tr, dict(d_output=1, output_activation=None), 136).to(DEV).train()
 
 
-@pytest.mark.parametrize("encoder_cfg,dropout", [(True, 0.1), (True, 0.0), (False, 0.2)])
+@pytest.mark.parametrize("encoder_cfg,dropout", [(True, 0.1), (True, 0.0), (False, 0.2), ("small_step", 0.1)])
 def test_graphed_training_step_equals_eager_steps(enc, monkeypatch, encoder_cfg, dropout):
+    """encoder_cfg "small_step": 16 slates of 256 documents on the default FFN path (GEMMs, split-K ks = 4 for the (T, d, d_ff) ones), captured."""
     from losses.approxNDCG import approxNDCGLoss
     from ltr_mi355x import blocks
     from ltr_mi355x.graphs import GraphedTrainStep
@@ -67,7 +74,13 @@ def test_graphed_training_step_equals_eager_steps(enc, monkeypatch, encoder_cfg,
     from architeture.multiLayer import LTRModel
     monkeypatch.setattr(blocks, "fresh_seed", lambda: SEED)        # the host seed every launch is recorded with
     monkeypatch.setattr(LTRModel, "_ltr_next_seed", lambda self: SEED)
-    B, S = 24, 64
+    B, S = (16, 256) if encoder_cfg == "small_step" else (24, 64)
+    calls = None
+    if encoder_cfg == "small_step":
+        from test_encoder_gpu import FfnCalls
+        monkeypatch.delenv("LTR_ENC_FUSED_FFN", raising=False)
+        assert not enc.fused_ffn_enabled(128, 2048, B * S) and enc._small_step_splits(B * S, 128, 2048) == 4
+        calls = FfnCalls(monkeypatch, enc)
     gen = torch.Generator(device=DEV).manual_seed(1)
     x = torch.randn(B, S, 136, device=DEV, generator=gen)
     y = torch.randint(0, 5, (B, S), device=DEV, generator=gen).float()
@@ -76,6 +89,8 @@ def test_graphed_training_step_equals_eager_steps(enc, monkeypatch, encoder_cfg,
     y[3, 50:] = -1.0
 
     def loss_fn(net, x, mask, y):
+        if calls is not None:
+            calls.reset()           # after the capture: what the captured step recorded (forward here, backward after the return)
         return approxNDCGLoss(net(x, mask, None), y)
 
     net_g = _net(encoder_cfg, dropout)
@@ -85,6 +100,8 @@ def test_graphed_training_step_equals_eager_steps(enc, monkeypatch, encoder_cfg,
     E0 = 1000
     enc.seed_set(E0)
     step = GraphedTrainStep(net_g, opt_g, loss_fn, (x, mask, y), warmup=2)      # two real steps (epochs E0+1, E0+2); the capture runs nothing
+    if calls is not None:
+        calls.assert_gemm_path(B * S, 128, 2048, 2, 4, dropout)
     losses_g = [float(step(x, mask, y).detach()) for _ in range(3)]              # epochs E0+3 .. E0+5
     assert enc.seed_get() == E0 + 5
     losses_e = []
