@@ -426,26 +426,51 @@ __device__ __forceinline__ float apply_act_grad(float g, float h) {
 }
 
 // Per-wave dW tile sets, fixed at compile time.  The NR x NC tile grid is walked in row bands of height BH,
-// column-major inside a band; wave W owns the contiguous run [W*TW, W*TW+TW) of that walk: a compact ~BH x TW/BH
-// block whose A (row) and B (column) fragments are shared between its tiles.
+// column-major inside a band; wave W owns the contiguous run [dw_first(W), dw_first(W) + dw_count(W)) of that walk: a
+// compact ~BH x TW/BH block whose A (row) and B (column) fragments are shared between its tiles.
 template <int NR, int NC, int BH>
 __host__ __device__ constexpr int dw_row(int g) { return (g / (NC * BH)) * BH + (g % (NC * BH)) % BH; }
 template <int NR, int NC, int BH>
 __host__ __device__ constexpr int dw_col(int g) { return (g % (NC * BH)) / BH; }
+// Run lengths balanced per SIMD: waves W and W + 4 share a SIMD (and its matrix pipe), so the NW tiles are split into four
+// SIMD totals that differ by at most one, each total between the SIMD's two waves (the older wave takes the odd tile).
+// No wave gets more than ceil(NW / 8) = TW tiles, so the accumulator arrays keep their size.
+__host__ __device__ constexpr int dw_count(int NW, int W) {
+    const int s = W % (kWaves / 2), simd = NW / (kWaves / 2) + (s < NW % (kWaves / 2) ? 1 : 0);
+    return W < kWaves / 2 ? (simd + 1) / 2 : simd / 2;
+}
+__host__ __device__ constexpr int dw_first(int NW, int W) {
+    int g = 0;
+    for (int v = 0; v < W; ++v) g += dw_count(NW, v);
+    return g;
+}
+__host__ __device__ constexpr bool dw_sets_balanced(int NW) {
+    const int TW = (NW + kWaves - 1) / kWaves;
+    int lo = NW, hi = 0;
+    for (int s = 0; s < kWaves / 2; ++s) {
+        const int t = dw_count(NW, s) + dw_count(NW, s + kWaves / 2);
+        lo = t < lo ? t : lo;
+        hi = t > hi ? t : hi;
+        if (dw_count(NW, s) > TW || dw_count(NW, s + kWaves / 2) > TW) return false;
+    }
+    return hi - lo <= 1 && dw_first(NW, kWaves) == NW;
+}
 
 // dW tiles of wave W += A^T B over one 64-document chunk.
 //   a_base / b_base: this lane's LDS addresses of A[row q][16*0 + i] / B[row q][16*0 + i] for k-step 0;
 //   k-step s adds 4*LD floats; tile (To, Ti) adds 16*To / 16*Ti floats: all immediates.
 template <int W, int TW, int NR, int NC, int BH>
 struct DwSet {   // which A (row) / B (column) fragments wave W's tile set touches
+    static_assert(dw_sets_balanced(NR * NC) && TW == (NR * NC + kWaves - 1) / kWaves, "unbalanced dW tile sets");
+    static constexpr int first = dw_first(NR * NC, W), count = dw_count(NR * NC, W);
     static constexpr bool uses_row(int To) {
-        for (int j = 0; j < TW; ++j)
-            if (W * TW + j < NR * NC && dw_row<NR, NC, BH>(W * TW + j) == To) return true;
+        for (int j = 0; j < count; ++j)
+            if (dw_row<NR, NC, BH>(first + j) == To) return true;
         return false;
     }
     static constexpr bool uses_col(int Ti) {
-        for (int j = 0; j < TW; ++j)
-            if (W * TW + j < NR * NC && dw_col<NR, NC, BH>(W * TW + j) == Ti) return true;
+        for (int j = 0; j < count; ++j)
+            if (dw_col<NR, NC, BH>(first + j) == Ti) return true;
         return false;
     }
     static constexpr int n_frags() {
@@ -454,11 +479,7 @@ struct DwSet {   // which A (row) / B (column) fragments wave W's tile set touch
         for (int t = 0; t < NC; ++t) n += uses_col(t) ? 1 : 0;
         return n;
     }
-    static constexpr int n_tiles() {
-        int n = 0;
-        for (int j = 0; j < TW; ++j) n += (W * TW + j < NR * NC) ? 1 : 0;
-        return n;
-    }
+    static constexpr int n_tiles() { return count; }
 };
 
 template <int W, int TW, int NR, int NC, int BH, int LD>
@@ -474,9 +495,9 @@ __device__ __forceinline__ void dw_load(float (&af)[NR], float (&bf)[NC], const 
 template <int W, int TW, int NR, int NC, int BH>
 __device__ __forceinline__ void dw_mfma(f32x4 (&acc)[TW], const float (&af)[NR], const float (&bf)[NC]) {
 #pragma unroll
-    for (int j = 0; j < TW; ++j) {
-        const int g = W * TW + j;
-        if (g < NR * NC) acc[j] = mfma4(af[dw_row<NR, NC, BH>(g)], bf[dw_col<NR, NC, BH>(g)], acc[j]);
+    for (int j = 0; j < DwSet<W, TW, NR, NC, BH>::count; ++j) {
+        const int g = DwSet<W, TW, NR, NC, BH>::first + j;
+        acc[j] = mfma4(af[dw_row<NR, NC, BH>(g)], bf[dw_col<NR, NC, BH>(g)], acc[j]);
     }
 }
 
@@ -616,9 +637,9 @@ __device__ __forceinline__ void dw_chunk_h_w(f32x4 (&acc)[TW], const uint16_t *a
             if (S::uses_col(Ti)) {
                 const h16x8 bh = tr_frag_h<LDH>(bhi, 32 * s, Ti), bl = tr_frag_h<LDH>(blo, 32 * s, Ti);
 #pragma unroll
-                for (int j = 0; j < TW; ++j) {
-                    const int g = W * TW + j;
-                    if (g < NR * NC && dw_col<NR, NC, BH>(g) == Ti) {
+                for (int j = 0; j < S::count; ++j) {
+                    const int g = S::first + j;
+                    if (dw_col<NR, NC, BH>(g) == Ti) {
                         const int r = dw_row<NR, NC, BH>(g);
                         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], bh, acc[j], 0, 0, 0);
                         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], bl, acc[j], 0, 0, 0);
@@ -696,13 +717,11 @@ __device__ __forceinline__ int grow_exp(int ex, float m) {
 template <int W, int TW, int NR, int NC, int BH>
 __device__ __forceinline__ void dw_store_w(const f32x4 (&acc)[TW], float *dst, int q, int d, float scale) {
 #pragma unroll
-    for (int j = 0; j < TW; ++j) {
-        const int g = W * TW + j;
-        if (g < NR * NC) {
-            const int To = dw_row<NR, NC, BH>(g), Ti = dw_col<NR, NC, BH>(g);
+    for (int j = 0; j < DwSet<W, TW, NR, NC, BH>::count; ++j) {
+        const int g = DwSet<W, TW, NR, NC, BH>::first + j;
+        const int To = dw_row<NR, NC, BH>(g), Ti = dw_col<NR, NC, BH>(g);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) dst[(16 * To + 4 * q + r) * (NC * 16) + 16 * Ti + d] = acc[j][r] * scale;
-        }
+        for (int r = 0; r < 4; ++r) dst[(16 * To + 4 * q + r) * (NC * 16) + 16 * Ti + d] = acc[j][r] * scale;
     }
 }
 
@@ -767,9 +786,9 @@ __device__ __forceinline__ void load_x_tile(f32x4 (&xr)[kXV4<N>()], const PipeAr
 // X: HBM/L2 -> LDS by LDS-DMA (global_load_lds, 16 B per lane, no VGPRs, no address math): one wave-instruction
 // per document row, lanes 0..F/4-1 active, destination = row base + lane*16 (rows keep their padded LD stride;
 // the pad columns -- ones feature + zeros -- are constant and written once per kernel).  Rows past the end of
-// the batch are zero-filled.  Issued and waited for at the top of a tile, with no other vector-memory load in
-// flight: while an LDS-DMA is pending hipcc turns every vmcnt wait into vmcnt(0), so overlapping it with the
-// weight-fragment ring or the dW GEMMs costs more than it hides (measured, profiles/r01_variant_ab.json).
+// the batch are zero-filled.  Never in flight under the weight-fragment ring: while an LDS-DMA is pending hipcc turns
+// every vmcnt wait into vmcnt(0), so overlapping it with fc1 / fc2 / dh1 costs more than it hides (measured,
+// profiles/r01_variant_ab.json).  The 136-wide backward kernels issue it after dW1 (REORD), the others at the tile top.
 template <class N>
 __device__ __forceinline__ void dma_x_rows(const PipeArgs &a, float *Xs, long long row0, int w, int lane) {
     typedef __attribute__((address_space(1))) const void *gptr_t;
@@ -783,6 +802,40 @@ __device__ __forceinline__ void dma_x_rows(const PipeArgs &a, float *Xs, long lo
         } else if (lane < N::F / 4) {
             *reinterpret_cast<f32x4 *>(dst + 4 * lane) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
+    }
+}
+
+// dW2 += dz2^T [h1 | 1] over the super-tile's two 64-document chunks: the waves of chunk c (c = w >> 2) stage their dz2 and h1
+// tiles in Ds / Hs, then every wave runs its dW2 tiles over the chunk (chunk 0, then chunk 1).  Reads LDS only.
+template <class N, class Stamp>
+__device__ __forceinline__ void dw2_chunks(int w, int chunk, int crow, int q, int d, const f32x4 (&dz2)[N::NT2], const f32x4 (&h1)[N::H1T],
+                                           f32x4 (&acc)[N::TW2], float *Ds, float *Hs, Stamp stamp) {
+    constexpr int LD = N::LD;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        if (c > 0) __syncthreads();   // chunk 0 fully consumed
+        if (chunk == c) {
+#pragma unroll
+            for (int To = 0; To < N::NT2; ++To)
+                *reinterpret_cast<f32x4 *>(Ds + crow * LD + 16 * To + ((4 * q) ^ (LTR_STG_SWZ ? 4 * ((crow >> 1) & 3) : 0))) = dz2[To];
+#pragma unroll
+            for (int T = 0; T < N::H1T; ++T)
+                *reinterpret_cast<f32x4 *>(Hs + crow * LD + 16 * T + ((4 * q) ^ (LTR_STG_SWZ ? 4 * ((crow >> 1) & 3) : 0))) = h1[T];
+        }
+#ifdef LTR_STAMPS_DW
+        stamp(c == 0 ? 10 : 13);
+#endif
+        __syncthreads();
+#ifdef LTR_STAMPS_DW
+        stamp(c == 0 ? 11 : 14);
+#endif
+        dw_chunk<N::TW2, N::NT2, N::H1T, N::BH2, LD>(w, acc, Ds + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (q >> 1) : 0)),
+                                                     Hs + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (q >> 1) : 0)),
+                                                     Ds + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (2 + (q >> 1)) : 0)),
+                                                     Hs + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (2 + (q >> 1)) : 0)));
+#ifdef LTR_STAMPS_DW
+        if (c == 0) stamp(12);
+#endif
     }
 }
 
@@ -862,6 +915,15 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
 #else
     constexpr bool DWH = false;
 #endif
+    // Backward order of the three-layer LDS-DMA kernels (exact path): dz2 -> dh1 -> dz1 -> dW1, then the next super-tile's X is
+    // issued into Xs (free once dW1 has read it) ahead of dW2, which reads nothing but the Ds / Hs staging images; the tile top
+    // then only waits for it.  Every dW tile still sums its documents in the same order (chunk 0, then chunk 1), so no result
+    // bit changes.  The fence of the first dW2 __syncthreads() waits for the DMA, so it lands under the chunk-0 staging; an
+    // LDS-only barrier there was measured 0.3 % slower.
+#ifndef LTR_REORD
+#define LTR_REORD 1
+#endif
+    constexpr bool REORD = LTR_REORD && XDMA && !N::TWO && !DWH && MODE != MODE_FWD;
     f32x4 xn[kXV4<N>()];
 #if LTR_F16X2
     if (DWH) {    // zero pad columns of both X images (the ones feature at column F is rewritten per tile: it carries the scale)
@@ -940,7 +1002,8 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
         }
 #endif
         LTR_STAMP(0)
-        __syncthreads();   // previous super-tile done with Xs / sc / dsc
+        // previous super-tile done with Xs / sc / dsc (REORD: its last barrier, before the X issue, already ordered all of them)
+        if (!REORD) __syncthreads();
         // ---- X: HBM -> LDS, coalesced 16 B per lane; the wave's 16 documents are contiguous in memory.
 #if LTR_F16X2
         if (DWH && XPREF) {
@@ -960,7 +1023,7 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
         } else
 #endif
         if (XDMA) {
-            dma_x_rows<N>(a, Xs, doc_base + 16 * w, w, lane);
+            if (!REORD || st == (int)blockIdx.x) dma_x_rows<N>(a, Xs, doc_base + 16 * w, w, lane);   // REORD: issued under dW2
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else {
             // register-prefetch kernels: only the first tile is loaded here, later ones arrive ahead of time
@@ -1155,7 +1218,7 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
         // ---- pull the NEXT super-tile of X into L2 while this one is in its backward (one dword per 128-B line
         //      per lane; the value is only kept alive until the end of the iteration so the load is waited for)
         float pf = 0.f;
-        if (!XPREF) {
+        if (!XPREF && !REORD) {
             const long long nb = (long long)(st + gridDim.x) * kTileDocs;
             const long long fl = nb * N::F + (long long)tid * 32;          // float index of this lane's line
             if (st + (int)gridDim.x < a.n_super && fl < a.n_docs * N::F) pf = a.X[fl];
@@ -1200,6 +1263,7 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
         }
 #endif
         LTR_STAMP(6)
+        auto stamp_dw = [&](int k) { LTR_STAMP(k) };
 #if LTR_F16X2
         if (DWH && !N::TWO) {
             // operand scales of dW2 (running maxima): h1 from the per-wave maxima published before the loss barrier; dz2 from
@@ -1246,34 +1310,10 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
         } else
 #endif
         // ---- dW2 += dz2^T [h1 | 1] over the two 64-document chunks (tiles of waves 0-3, then waves 4-7)
-#pragma unroll
-        for (int c = 0; c < (N::TWO ? 0 : 2); ++c) {
-            if (c > 0) __syncthreads();   // chunk 0 fully consumed
-            if (chunk == c) {
-#pragma unroll
-                for (int To = 0; To < N::NT2; ++To)
-                    *reinterpret_cast<f32x4 *>(Ds + crow * LD + 16 * To + ((4 * q) ^ (LTR_STG_SWZ ? 4 * ((crow >> 1) & 3) : 0))) = h2[To];
-#pragma unroll
-                for (int T = 0; T < N::H1T; ++T)
-                    *reinterpret_cast<f32x4 *>(Hs + crow * LD + 16 * T + ((4 * q) ^ (LTR_STG_SWZ ? 4 * ((crow >> 1) & 3) : 0))) = h1[T];
-            }
-#ifdef LTR_STAMPS_DW
-            if (c == 0) { LTR_STAMP(10) } else { LTR_STAMP(13) }
-#endif
-            __syncthreads();
-#ifdef LTR_STAMPS_DW
-            if (c == 0) { LTR_STAMP(11) } else { LTR_STAMP(14) }
-#endif
-            if (!LTR_SKIP(a, 2))
-                dw_chunk<N::TW2, N::NT2, N::H1T, N::BH2, LD>(w, accW2, Ds + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (q >> 1) : 0)),
-                                                             Hs + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (q >> 1) : 0)),
-                                                             Ds + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (2 + (q >> 1)) : 0)),
-                                                             Hs + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (2 + (q >> 1)) : 0)));
-#ifdef LTR_STAMPS_DW
-            if (c == 0) { LTR_STAMP(12) }
-#endif
+        if (!REORD) {
+            if (!N::TWO && !LTR_SKIP(a, 2)) dw2_chunks<N>(w, chunk, crow, q, d, h2, h1, accW2, Ds, Hs, stamp_dw);
+            LTR_STAMP(7)
         }
-        LTR_STAMP(7)
         // ---- dh1^T = W2^T dz2^T  (A = packed W2^T fragments, B = dz2 registers), then
         //      dz1 = dh1 * act1'(h1), features >= H1 (incl. the ones feature) zeroed
         f32x4 dz1[N::NT1];
@@ -1304,7 +1344,7 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
                 if (16 * To + 16 > N::H1) v = (16 * To + 4 * q + r < N::H1) ? v : 0.f;   // last tile only
                 dz1[To][r] = v;
             }
-        LTR_STAMP(8)
+        if (REORD) { LTR_STAMP(7) } else { LTR_STAMP(8) }
 #if LTR_F16X2
         if (DWH) {
             float m = 0.f;
@@ -1352,7 +1392,7 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
             // dW2 is done with the two staging buffers, which are contiguous (Ds..Hs = one [128][LD] region): every
             // wave stages its dz1 tile at once, one barrier, then both 64-document halves back to back.  (-3.5 % on
             // the 136-64-32 net; on the register-bound 136-136-136 kernels the chunked form below is faster.)
-            __syncthreads();              // every wave is done reading Ds / Hs (dW2 chunk 1)
+            if (!REORD) __syncthreads();  // every wave is done reading Ds / Hs (dW2 chunk 1)
 #pragma unroll
             for (int To = 0; To < N::NT1; ++To)
                 *reinterpret_cast<f32x4 *>(Ds + my_row * LD + 16 * To + ((4 * q) ^ (LTR_STG_SWZ ? 4 * ((my_row >> 1) & 3) : 0))) = dz1[To];
@@ -1381,6 +1421,13 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
                                                                 Ds + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (2 + (q >> 1)) : 0)),
                                                                 Xs + (64 * c + q) * LD + d);
             }
+        }
+        if (REORD) {
+            LTR_STAMP(8)
+            __syncthreads();              // every wave is done reading Xs and Ds..Hs (dW1)
+            // next super-tile's X -> Xs (no X read until the wait at the tile top)
+            if (st + (int)gridDim.x < a.n_super) dma_x_rows<N>(a, Xs, (long long)(st + gridDim.x) * kTileDocs + 16 * w, w, lane);
+            if (!LTR_SKIP(a, 2)) dw2_chunks<N>(w, chunk, crow, q, d, h2, h1, accW2, Ds, Hs, stamp_dw);
         }
 #if LTR_F16X2
         }

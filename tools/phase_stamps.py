@@ -11,14 +11,21 @@ from ltr_mi355x import lib, scorer  # noqa: E402
 from ltr_mi355x.extra_nets import TwoLayerNet  # noqa: E402
 from ltr_mi355x.functional import _ptr, _stream, check  # noqa: E402
 
-NAMES = ["barrier+X load->LDS", "fc1 (+act)", "fc2 (+act)", "fc3+scores", "loss", "L2 prefetch+dw3+dz2",
-         "dW2 (2 chunks)", "dh1 (+mask)", "dW1 (2 chunks)"]
+# Phase order of the 136-wide backward: dz2 -> dh1 -> dW1, then the next X tile is issued and lands under dW2, so the
+# tile top only waits for it.  --old-order reads a library built before that change (L2 prefetch, dW2 before dh1).
+# The 136-64-32 net keeps the old order.
+OLD_ORDER = "--old-order" in sys.argv[1:]
+OLD_NAMES = ["barrier+X load->LDS", "fc1 (+act)", "fc2 (+act)", "fc3+scores", "loss", "L2 prefetch+dw3+dz2",
+             "dW2 (2 chunks)", "dh1 (+mask)", "dW1 (2 chunks)"]
+NEW_NAMES = ["X wait+labels barrier", "fc1 (+act)", "fc2 (+act)", "fc3+scores", "loss", "dw3+dz2", "dh1 (+mask)",
+             "dz1 staging+dW1 (2 chunks)", "barrier+next X issue+dW2 (2 chunks)"]
 dev = torch.device("cuda:0")
 B, S = 25_000, 128
 X = torch.randn(B, S, 136, device=dev)
 y = torch.randint(0, 5, (B, S), device=dev).float()
 h = lib()
 for name, cls in (("double", DoubleLayerNet), ("triple", TripleLayerNet)):      # the 136-64-1 net: tools/fcw_stamps.py
+    NAMES = NEW_NAMES if name == "double" and not OLD_ORDER else OLD_NAMES
     net = cls(136).to(dev).eval()
     info = scorer.NetInfo.get(net._ltr_net)
     packed = scorer.pack_params(net._ltr_net, net._ltr_params())
