@@ -112,6 +112,20 @@ int ltr_lambda_colsum_sys_fwd(const float *y_pred, const float *y_true, const fl
  * grad_colsum [B][S] = d L / d colsum[0] -> dy_pred [B][S]. */
 int ltr_lambda_colsum_sys_bwd(const float *y_pred, const float *y_true, int B, int S, int scheme, int k, float sigma, float mu,
                               float eps, float pad, int log_base, const float *grad_colsum, float *dy_pred, void *stream);
+/* The same backward with d L / d colsum[0][b][j] = jac[b][j] * coef[b * coef_stride] formed inside the launch: jac = d mat[b][0] / d colsum
+ * (ltr_risk_matrix_fwd / ltr_lambda_risk_model_fwd), coef = the model column of the tail's d L / d mat, read in place (coef_stride = the
+ * matrix row length). */
+int ltr_lambda_colsum_sys_bwd_coef(const float *y_pred, const float *y_true, int B, int S, int scheme, int k, float sigma, float mu,
+                                   float eps, float pad, int log_base, const float *jac, const float *coef, int coef_stride, float *dy_pred,
+                                   void *stream);
+/* A Lambda-type risk matrix with the constant systems cached (the fused risk step's baseline columns): per query b, cache[b * cache_stride ..]
+ * = [n_cached matrix entries (baselines, ideal ranking, ones column) | the ideal ranking's column sums [S]].  One launch: the MODEL's
+ * column sums (softmaxes inside, as ltr_lambda_colsum_sys_fwd system 0), its effectiveness against the cached ideal column sums
+ * (lt 1 / 2 / 3, as ltr_risk_matrix_fwd mode 1), jac [B][S] = d mat[b][0] / d colsum, and the row mat[b] = [model | cached entries]
+ * ([B][1 + n_cached]).  Bitwise the matrix of ltr_lambda_colsum_sys_fwd + ltr_risk_matrix_fwd.  2 <= S <= 2048. */
+int ltr_lambda_risk_model_fwd(const float *y_pred, const float *y_true, const float *cache, int cache_stride, int n_cached, int B, int S,
+                              int scheme, int k, float sigma, float mu, float eps, float pad, int log_base, int lt, float *mat, float *jac,
+                              void *stream);
 
 /* ---- zRisk / geoRisk(mat, alpha, requires_grad, i)          losses/riskLosses/riskFunctions.py:4-22 / :25-33
  * mat[Q][n_systems]: effectiveness of every system (column) on every query (row); col = the system under test
@@ -157,6 +171,24 @@ int ltr_trisk_tail_fwd_bwd(const float *mat, int Q, float alpha, int flip, float
  * The caller applies the `-mat + max(mat)` flip of lt 1 / 3 (:47-49; a whole-matrix maximum).  S <= 2048. */
 int ltr_risk_matrix_fwd(const float *ref, const float *x0, const float *rest, int B, int S, int n_rest, int mode, int lt, int ideal,
                         float *mat, float *jac, void *stream);
+/* As ltr_risk_matrix_fwd; ones != 0 appends one more column of 1.0 (geoRiskLambdaLoss's ideal ranking under transformation 2,
+ * riskLosses.py:106): mat [B][1 + n_rest + (ideal != 0) + (ones != 0)]. */
+int ltr_risk_matrix_rows_fwd(const float *ref, const float *x0, const float *rest, int B, int S, int n_rest, int mode, int lt, int ideal,
+                             int ones, float *mat, float *jac, void *stream);
+/* As ltr_risk_matrix_fwd with the constant columns given: mat[b] = [model | cached[b * cache_stride + 0 .. n_cached)], only the model's
+ * entry (and jac) computed.  mode 0 / 2 (Listnet type); the cached entries come from an earlier ltr_risk_matrix_fwd call. */
+int ltr_risk_matrix_cached_fwd(const float *ref, const float *x0, const float *cached, int cache_stride, int B, int S, int n_cached,
+                               int mode, int lt, float *mat, float *jac, void *stream);
+/* dscores[b][j] = jac[b][j] * dmat[b * dmat_stride]: the scores gradient of a risk loss from the model column of d L / d mat. */
+int ltr_risk_scores_grad(const float *jac, const float *dmat, int dmat_stride, int B, int S, float *dscores, void *stream);
+/* The two tails over an all-gathered, per-rank padded matrix (data-parallel risk step): n_blocks blocks of (1 + block_rows * n) floats,
+ * block k = its valid row count (as a float), then block_rows rows.  The valid rows, in block order, are the matrix; padded rows are
+ * neither read nor written, and the sums run in the order of the dense matrix (same bits as ltr_risk_tail_fwd_bwd /
+ * ltr_trisk_tail_fwd_bwd on it).  dmat has the blocks' layout.  n_blocks <= 1024. */
+int ltr_risk_tail_blocks_fwd_bwd(const float *blocks, int n_blocks, int block_rows, int n_systems, float alpha, int kind, int strategy,
+                                 int flip, float factor, int zquirk, float *value, float *dmat, void *stream);
+int ltr_trisk_tail_blocks_fwd_bwd(const float *blocks, int n_blocks, int block_rows, float alpha, int flip, float factor, float *value,
+                                  float *dmat, void *stream);
 
 /* ---- mNdcg / ndcg / dcg / torchNdcg                                            utils/metrics.py:48-104
  * Per-query NDCG@k on the device (the reference loops over queries in Python after every epoch,

@@ -408,12 +408,134 @@ lambda_colsum_sys_fwd_kernel(const float *__restrict__ y_pred, const float *__re
     }
 }
 
+// ---- The Lambda-type risk step with the constant systems cached (ltr_mi355x.scorer.FusedRanker.baseline_columns): the baselines' and the
+// ideal ranking's matrix entries and the ideal column sums depend on (y_true, y_base) only.  One workgroup per query runs the MODEL's
+// column sums (slate softmaxes inside, as lambda_colsum_sys_fwd_kernel system 0), then its effectiveness against the cached ideal
+// column sums and d mat[b][0] / d colsum (ltr_risk_matrix_fwd mode 1, column 0), and copies the cached entries into the row.
+// Bitwise the same matrix as the two uncached launches: the column sums run with the same group size, and the effectiveness sums
+// replay risk_matrix_kernel's 256-thread order (per-thread strides of 256, wave butterflies, four waves summed in order; with fewer
+// than 256 threads S <= group, so the missing threads would have held zeros).
+constexpr int kEffThreads = 256;
+
+__device__ __forceinline__ double eff_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, LTR_WAVE);
+    return v;
+}
+__device__ __forceinline__ double eff_block_sum(double v, double *red, int nw) {
+    v = eff_wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & (LTR_WAVE - 1)) == 0 && threadIdx.x < kEffThreads) red[threadIdx.x / LTR_WAVE] = v;
+    __syncthreads();
+    double s = 0.0;
+    for (int w = 0; w < kEffThreads / LTR_WAVE; ++w) s += w < nw ? red[w] : 0.0;
+    return s;
+}
+
+template <int SCH>
+__global__ void __launch_bounds__(1024)
+lambda_risk_model_fwd_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, const float *__restrict__ cache,
+                             int cache_stride, int n_cached, int B, int S, int group, LambdaParams P, float pad, int lt,
+                             float *__restrict__ mat, float *__restrict__ jac) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ double red[kEffThreads / LTR_WAVE];
+    const int s_al = (S + 3) & ~3;
+    const long long slate = ltr_block_id();
+    if (slate >= B) return;                      // (whole block: the y-padding of a two-dimensional grid)
+    float *base = smem;
+    const LambdaLds L = lambda_carve(base, s_al);
+    int *dar = reinterpret_cast<int *>(base + kLambdaArrays * s_al);   // document at rank r
+    float *x = base + (kLambdaArrays + 1) * s_al;                       // the model's column sums, by predicted rank
+    const SlateGroup g = make_group(S, group, x + s_al);
+    const size_t off = (size_t)slate * S;
+    const float *crow = cache + (size_t)slate * cache_stride;           // [n_cached matrix entries | ideal column sums [S]]
+    const float *t = crow + n_cached;
+    const int nsys = 1 + n_cached;
+    for (int k = threadIdx.x; k < n_cached; k += group) mat[(size_t)slate * nsys + 1 + k] = crow[k];
+    for (int j = g.t; j < S; j += group) {
+        L.yl[j] = y_true[off + j];
+        L.sc[j] = y_pred[off + j];
+    }
+    __syncthreads();
+    slate_softmax(g, L.yl, S);
+    slate_softmax(g, L.sc, S);
+    for (int j = g.t; j < S; j += group) stage_label(L.yl[j], pad, L.yl[j], L.gn[j]);
+    __syncthreads();
+    lambda_prepare(g, L, P);
+    for (int j = g.t; j < S; j += group) dar[L.rk[j]] = j;
+    __syncthreads();
+    for (int rj = g.t; rj < S; rj += group) {
+        const int j = dar[rj];
+        const bool pj = L.gn[j] < 0.f;
+        const float sj = pj ? -INFINITY : L.sc[j];
+        const float Gj = fmaxf(L.gn[j], 0.f), ycj = fmaxf(L.yl[j], 0.f);
+        float acc = 0.f;
+        for (int ri = 0; ri < S; ++ri) {          // rank order: the order torch.sum(dim=1) walks the column in
+            const int i = dar[ri];
+            const bool pi = L.gn[i] < 0.f;
+            const float si = pi ? -INFINITY : L.sc[i];
+            float d = si - sj;
+            d = (d != d) ? 0.f : fminf(fmaxf(d, -1e8f), 1e8f);
+            float u, um;
+            sigmoid_pair(P.sigma * d, u, um);
+            const float Gi = fmaxf(L.gn[i], 0.f), yci = fmaxf(L.yl[i], 0.f);
+            float ell, dl;
+            lambda_pair_term(P, lambda_weight<SCH>(P, L.delta, L.rk[i], L.rk[j], L.invd[i], L.invd[j], L.w1[i], Gi, Gj, yci, ycj),
+                             u, um, ell, dl);
+            acc += ell;
+        }
+        x[rj] = acc;
+    }
+    __syncthreads();
+    // effectiveness of the model against the ideal column sums (risk_matrix_kernel, mode 1, system 0)
+    const int tid = threadIdx.x, nw = group / LTR_WAVE;
+    const bool act = tid < kEffThreads;
+    double nt_a = 0.0, st_a = 0.0;
+    if (act)
+        for (int j = tid; j < S; j += kEffThreads) {
+            const float tj = t[j];
+            nt_a += (double)tj * tj;
+            st_a += (double)tj;
+        }
+    const double nt = eff_block_sum(nt_a, red, nw), st = eff_block_sum(st_a, red, nw);
+    double a_a = 0.0, nx_a = 0.0, c_a = 0.0, sx_a = 0.0;
+    if (act)
+        for (int j = tid; j < S; j += kEffThreads) {
+            const float tj = t[j], xj = x[j];
+            a_a += (double)tj * xj;
+            nx_a += (double)xj * xj;
+            sx_a += (double)xj;
+            const float df = xj - tj;
+            c_a += (double)df * df;
+        }
+    const double a = eff_block_sum(a_a, red, nw), nx = eff_block_sum(nx_a, red, nw), c = eff_block_sum(c_a, red, nw),
+                 sx = eff_block_sum(sx_a, red, nw);
+    const double nrm_u = sqrt(nt), nrm_v = sqrt(nx);
+    const double den = (nrm_u > 1e-8 ? nrm_u : 1e-8) * (nrm_v > 1e-8 ? nrm_v : 1e-8);
+    double m;
+    if (lt == 1) m = c;
+    else if (lt == 2) m = a / den;
+    else m = (sx - st) * (sx - st);
+    if (tid == 0) mat[(size_t)slate * nsys] = (float)m;
+    const double nv_c = nrm_v > 1e-8 ? nrm_v : 1e-8;
+    const double inv_vv = nrm_v > 0.0 ? 1.0 / (nv_c * nrm_v) : 0.0;
+    for (int j = tid; j < S; j += group) {
+        const double tj = t[j], xj = x[j];
+        double gj;
+        if (lt == 1) gj = 2.0 * (xj - tj);
+        else if (lt == 2) gj = tj / den - m * xj * inv_vv;
+        else gj = 2.0 * (sx - st);
+        jac[off + j] = (float)gj;
+    }
+}
+
 // d L / d y_pred from d L / d colsum[system 0]: the pair backward on the soft-maxed vectors, then the softmax's Jacobian
 // (d p_i / d s_k = p_i (delta_ik - p_k)):  ds_k = p_k (dp_k - sum_i p_i dp_i)
 template <int SCH>
 __global__ void __launch_bounds__(1024)
 lambda_colsum_sys_bwd_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, int B, int S, int group, LambdaParams P,
-                             float pad, const float *__restrict__ gup, float *__restrict__ dy_pred) {
+                             float pad, const float *__restrict__ gup, const float *__restrict__ coef, int coef_stride,
+                             float *__restrict__ dy_pred) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int s_al = (S + 3) & ~3;
     const long long slate = ltr_block_id();
@@ -434,6 +556,8 @@ lambda_colsum_sys_bwd_kernel(const float *__restrict__ y_pred, const float *__re
     __syncthreads();
     lambda_prepare(g, L, P);
     const float *G = gup + off;
+    // coef != NULL: d L / d colsum[0] = gup (the Jacobian of the model's matrix entry) x coef[slate] (d L / d mat[slate][0])
+    const float cq = coef ? coef[slate * coef_stride] : 1.f;
     for (int i0 = 0; i0 < S; i0 += g.sp) {
         const int i = i0 + g.ri;
         const bool row = i < S;
@@ -456,7 +580,7 @@ lambda_colsum_sys_bwd_kernel(const float *__restrict__ y_pred, const float *__re
                                  u, um, ell, dl_ij);
                 lambda_pair_term(P, lambda_weight<SCH>(P, L.delta, rj, ri, L.invd[j], L.invd[i], L.w1[j], Gj, Gi, ycj, yci),
                                  um, u, ell, dl_ji);
-                gr += G[rj] * dl_ij - G[ri] * dl_ji;
+                gr += (G[rj] * cq) * dl_ij - (G[ri] * cq) * dl_ji;
             }
         }
         const float tot = row_reduce(g, gr);
@@ -780,7 +904,48 @@ int ltr_lambda_colsum_sys_bwd(const float *y_pred, const float *y_true, int B, i
 #define CALL(SCH)                                                                                                 \
     if (int rc = allow_lds(lambda_colsum_sys_bwd_kernel<SCH>, lds)) return rc;                                    \
     hipLaunchKernelGGL(lambda_colsum_sys_bwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, y_pred, y_true, B, S, \
-                       group, P, pad, grad_colsum, dy_pred)
+                       group, P, pad, grad_colsum, nullptr, 0, dy_pred)
+    LTR_DISPATCH_SCHEME(scheme, CALL)
+#undef CALL
+    return launch_status();
+}
+
+int ltr_lambda_risk_model_fwd(const float *y_pred, const float *y_true, const float *cache, int cache_stride, int n_cached, int B, int S,
+                              int scheme, int k, float sigma, float mu, float eps, float pad, int log_base, int lt, float *mat, float *jac,
+                              void *stream) {
+    if (int rc = check_slates(y_pred, y_true, mat, B, S)) return rc;
+    if (!cache || !jac) return LTR_ERR_NULL;
+    if (S < 2 || S > 2048 || n_cached < 0 || n_cached > 65 || cache_stride < n_cached + S) return LTR_ERR_SHAPE;
+    if (lt < 1 || lt > 3) return LTR_ERR_PARAM;
+    LambdaParams P;
+    if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
+    if (B == 0) return LTR_OK;
+    const int group = next_pow2(S) < 64 ? 64 : (next_pow2(S) > 1024 ? 1024 : next_pow2(S));     // = ltr_lambda_colsum_sys_fwd's
+    const size_t lds = (size_t)((kLambdaArrays + 2) * ((S + 3) & ~3) + group + 32) * sizeof(float);
+#define CALL(SCH)                                                                                                 \
+    if (int rc = allow_lds(lambda_risk_model_fwd_kernel<SCH>, lds)) return rc;                                    \
+    hipLaunchKernelGGL(lambda_risk_model_fwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, y_pred, y_true, cache, \
+                       cache_stride, n_cached, B, S, group, P, pad, lt, mat, jac)
+    LTR_DISPATCH_SCHEME(scheme, CALL)
+#undef CALL
+    return launch_status();
+}
+
+int ltr_lambda_colsum_sys_bwd_coef(const float *y_pred, const float *y_true, int B, int S, int scheme, int k, float sigma, float mu,
+                                   float eps, float pad, int log_base, const float *jac, const float *coef, int coef_stride, float *dy_pred,
+                                   void *stream) {
+    if (int rc = check_slates(y_pred, y_true, dy_pred, B, S)) return rc;
+    if (!jac || !coef) return LTR_ERR_NULL;
+    if (coef_stride < 1) return LTR_ERR_SHAPE;
+    LambdaParams P;
+    if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
+    if (B == 0) return LTR_OK;
+    const int group = pick_group(S) < 256 ? 256 : pick_group(S);
+    const size_t lds = (size_t)((kLambdaArrays + 1) * ((S + 3) & ~3) + group + 32) * sizeof(float);
+#define CALL(SCH)                                                                                                 \
+    if (int rc = allow_lds(lambda_colsum_sys_bwd_kernel<SCH>, lds)) return rc;                                    \
+    hipLaunchKernelGGL(lambda_colsum_sys_bwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, y_pred, y_true, B, S, \
+                       group, P, pad, jac, coef, coef_stride, dy_pred)
     LTR_DISPATCH_SCHEME(scheme, CALL)
 #undef CALL
     return launch_status();

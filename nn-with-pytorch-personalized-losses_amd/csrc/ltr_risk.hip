@@ -134,19 +134,62 @@ trisk_kernel(const float *__restrict__ a, const float *__restrict__ b, int Q, fl
     }
 }
 
+// Row maps of the two tails.  A dense matrix is ONE block of Q rows.  The data-parallel risk step (ltr_mi355x.scorer.FusedRanker under
+// ltr_mi355x.dp.QueryShardedTrainer) hands the tails the all-gathered per-rank blocks instead: block k = one float holding its row
+// count, then `block_rows` rows of n floats (a rank's rows, padded to the largest shard).  Logical row q runs over the valid rows only,
+// in block order, so a padded gather is summed in exactly the order of the dense matrix it stands for.  The counts are read on the
+// device: no host round trip for ragged shards.
+constexpr int kMaxRowBlocks = 1024;
+struct RowBlocks {
+    const int *pre;     // LDS [n_blocks + 1]: prefix sums of the block row counts
+    int n_blocks, stride, hdr, n, Q;
+    __device__ __forceinline__ size_t row(int q) const {     // offset of logical row q's first element
+        int lo = 0, hi = n_blocks - 1;
+        while (lo < hi) {                                     // the last block k with pre[k] <= q
+            const int mid = (lo + hi + 1) >> 1;
+            if (pre[mid] <= q) lo = mid; else hi = mid - 1;
+        }
+        return (size_t)lo * stride + hdr + (size_t)(q - pre[lo]) * n;
+    }
+};
+// all threads call it (one barrier inside)
+__device__ __forceinline__ RowBlocks row_blocks(int n_blocks, int block_rows, int n, int hdr, const float *base, int *pre) {
+    RowBlocks rb;
+    rb.stride = hdr + block_rows * n;
+    if (threadIdx.x == 0) {
+        int acc = 0;
+        for (int k = 0; k < n_blocks; ++k) {
+            pre[k] = acc;
+            int c = hdr ? (int)base[(size_t)k * rb.stride] : block_rows;
+            acc += c < 0 ? 0 : (c > block_rows ? block_rows : c);
+        }
+        pre[n_blocks] = acc;
+    }
+    __syncthreads();
+    rb.pre = pre;
+    rb.n_blocks = n_blocks;
+    rb.hdr = hdr;
+    rb.n = n;
+    rb.Q = pre[n_blocks];
+    return rb;
+}
+
 // The TAIL of a tRisk loss in one launch (riskLosses.py:269-291 / :332-345) on the [Q][2] matrix (model, baseline): the flip of
 // transformation 1 (mat' = -mat + max(mat), in the reference's fp32 arithmetic), the alpha-weighted deltas, mean / std, the
 // `negative` factor; value and d value / d mat together.  The flip's whole-matrix maximum gets no gradient: the gradients of the
 // two columns of a query are g and -g, so their sum over the matrix is zero.
 __global__ void __launch_bounds__(kRiskThreads)
-trisk_tail_kernel(const float *__restrict__ mat, int Q, float alpha, int flip, float factor, float *__restrict__ value,
-                  float *__restrict__ dmat) {
+trisk_tail_kernel(const float *__restrict__ mat, int n_blocks, int block_rows, int hdr, float alpha, int flip, float factor,
+                  float *__restrict__ value, float *__restrict__ dmat) {
     __shared__ double red[kRiskThreads / LTR_WAVE];
+    __shared__ int pre[kMaxRowBlocks + 1];
     const int tid = threadIdx.x;
+    const RowBlocks rb = row_blocks(n_blocks, block_rows, 2, hdr, mat, pre);
+    const int Q = rb.Q;
     float M = 0.f;
     if (flip) {
         float mx = -INFINITY;
-        for (int e = tid; e < 2 * Q; e += kRiskThreads) mx = fmaxf(mx, mat[e]);
+        for (int e = tid; e < 2 * Q; e += kRiskThreads) mx = fmaxf(mx, mat[rb.row(e >> 1) + (e & 1)]);
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, LTR_WAVE));
         __syncthreads();
@@ -156,7 +199,7 @@ trisk_tail_kernel(const float *__restrict__ mat, int Q, float alpha, int flip, f
         for (int w = 1; w < kRiskThreads / LTR_WAVE; ++w) M = fmaxf(M, (float)red[w]);
         __syncthreads();
     }
-    auto at = [&](int q, int j) -> float { return flip ? -mat[2 * (size_t)q + j] + M : mat[2 * (size_t)q + j]; };
+    auto at = [&](int q, int j) -> float { return flip ? -mat[rb.row(q) + j] + M : mat[rb.row(q) + j]; };
     double s = 0.0;
     for (int q = tid; q < Q; q += kRiskThreads) {
         const float a = at(q, 0), b = at(q, 1);
@@ -178,8 +221,9 @@ trisk_tail_kernel(const float *__restrict__ mat, int Q, float alpha, int flip, f
         const double c = a < b ? 1.0 + (double)alpha : 1.0;
         const double x = ((double)a - (double)b) * c;
         const float g = (float)((1.0 / ((double)Q * se) - mu * (x - mu) / ((double)(Q - 1) * se * var)) * c) * factor;
-        dmat[2 * (size_t)q] = flip ? -g : g;
-        dmat[2 * (size_t)q + 1] = flip ? g : -g;
+        const size_t r = rb.row(q);
+        dmat[r] = flip ? -g : g;
+        dmat[r + 1] = flip ? g : -g;
     }
 }
 
@@ -199,14 +243,18 @@ inline int status() {
 struct RiskCol { double si, Z, T1, val, dZ, dSi; };
 
 __global__ void __launch_bounds__(kRiskThreads)
-risk_tail_kernel(const float *__restrict__ mat, int Q, int n, float alpha, int geo, int strategy, int flip, float factor, int zquirk,
+risk_tail_kernel(const float *__restrict__ mat, int n_blocks, int block_rows, int hdr, int n, float alpha, int geo, int strategy, int flip, float factor, int zquirk,
                  float *__restrict__ value, float *__restrict__ dmat) {
     __shared__ double red[kRiskThreads / LTR_WAVE];
+    __shared__ int pre[kMaxRowBlocks + 1];
     const int tid = threadIdx.x;
+    const RowBlocks rb = row_blocks(n_blocks, block_rows, n, hdr, mat, pre);
+    const int Q = rb.Q;
+    auto elem = [&](int e) -> size_t { const int q = e / n; return rb.row(q) + (e - q * n); };   // element e of the dense matrix
     double M = 0.0;
     if (flip) {
         double mx = -INFINITY;
-        for (int e = tid; e < Q * n; e += kRiskThreads) mx = fmax(mx, (double)mat[e]);
+        for (int e = tid; e < Q * n; e += kRiskThreads) mx = fmax(mx, (double)mat[elem(e)]);
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, LTR_WAVE));
         __syncthreads();
@@ -217,7 +265,7 @@ risk_tail_kernel(const float *__restrict__ mat, int Q, int n, float alpha, int g
         M = (double)(float)M;
     }
     // the flipped entry in the reference's fp32 arithmetic (-mat + max), then promoted
-    auto at = [&](int q, int j) -> double { return flip ? (double)(-mat[(size_t)q * n + j] + (float)M) : (double)mat[(size_t)q * n + j]; };
+    auto at = [&](int q, int j) -> double { return flip ? (double)(-mat[rb.row(q) + j] + (float)M) : (double)mat[rb.row(q) + j]; };
     const int ncol = strategy == 1 ? 1 : 2;
     const int cols[2] = {0, n - 1};
     RiskCol rc[2];
@@ -289,16 +337,16 @@ risk_tail_kernel(const float *__restrict__ mat, int Q, int n, float alpha, int g
             if (j == 0) gq += own[0];
             if (ncol > 1 && j == n - 1) gq += own[1];
             g_acc += gq;
-            dmat[(size_t)q * n + j] = (float)(flip ? -gq : gq);
+            dmat[rb.row(q) + j] = (float)(flip ? -gq : gq);
         }
     }
     if (flip) {      // d max(mat) / d mat: the sum of all d value / d mat' entries lands on the maximal entries
         const double G = block_sum_f64(g_acc, red);
         double ties_a = 0.0;
-        for (int e = tid; e < Q * n; e += kRiskThreads) ties_a += (double)mat[e] == M ? 1.0 : 0.0;
+        for (int e = tid; e < Q * n; e += kRiskThreads) ties_a += (double)mat[elem(e)] == M ? 1.0 : 0.0;
         const double ties = block_sum_f64(ties_a, red);
         for (int e = tid; e < Q * n; e += kRiskThreads)
-            if ((double)mat[e] == M) dmat[e] += (float)(G / ties);
+            if ((double)mat[elem(e)] == M) dmat[elem(e)] += (float)(G / ties);
     }
 }
 
@@ -353,11 +401,18 @@ __device__ __forceinline__ void mat_softmax(float *v, int S, double *red) {
 
 __global__ void __launch_bounds__(kMatThreads)
 risk_matrix_kernel(const float *__restrict__ ref, const float *__restrict__ x0, const float *__restrict__ rest, int B, int S, int nr,
-                   int mode, int lt, int ideal, float *__restrict__ mat, float *__restrict__ jac) {
+                   int mode, int lt, int ideal, int ones, const float *__restrict__ cached, int cache_stride, float *__restrict__ mat,
+                   float *__restrict__ jac) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ double red[kMatThreads / LTR_WAVE];
     float *t = smem, *x = smem + S;
-    const int b = blockIdx.x, tid = threadIdx.x, nsys = 1 + nr + (ideal ? 1 : 0);
+    // cached != NULL: columns 1 .. nr come from cached[b][0 .. nr) (the constant systems, ltr_risk_matrix_cached_fwd); only the model runs
+    // ones != 0: one more column of 1.0 after the computed ones (geoRiskLambdaLoss's ideal ranking under transformation 2, :106)
+    const int b = blockIdx.x, tid = threadIdx.x, nsys = 1 + nr + (ideal && !cached ? 1 : 0), nrun = cached ? 1 : nsys;
+    const int ld = nsys + (ones && !cached ? 1 : 0);
+    if (cached)
+        for (int k = tid; k < nr; k += kMatThreads) mat[(size_t)b * ld + 1 + k] = cached[(size_t)b * cache_stride + k];
+    if (ld > nsys && tid == 0) mat[(size_t)b * ld + nsys] = 1.0f;
     for (int j = tid; j < S; j += kMatThreads) t[j] = ref[(size_t)b * S + j];
     __syncthreads();
     if (mode != 1) mat_softmax(t, S, red);
@@ -367,8 +422,8 @@ risk_matrix_kernel(const float *__restrict__ ref, const float *__restrict__ x0, 
         st_a += (double)t[j];
     }
     const double nt = mat_block_sum(nt_a, red), st = mat_block_sum(st_a, red);
-    for (int sys = 0; sys < nsys; ++sys) {
-        const bool is_ideal = ideal && sys == nsys - 1;
+    for (int sys = 0; sys < nrun; ++sys) {
+        const bool is_ideal = ideal && !cached && sys == nsys - 1;
         __syncthreads();
         for (int j = tid; j < S; j += kMatThreads) {
             float v;
@@ -405,7 +460,7 @@ risk_matrix_kernel(const float *__restrict__ ref, const float *__restrict__ x0, 
         if (lt == 1) m = c;
         else if (lt == 2) m = ca / den;
         else m = mode == 1 ? (sx - st) * (sx - st) : (a - nt) * (a - nt);
-        if (tid == 0) mat[(size_t)b * nsys + sys] = (float)m;
+        if (tid == 0) mat[(size_t)b * ld + sys] = (float)m;
         if (sys == 0 && jac) {
             // g_j = d m / d x_j; mode 0: x = softmax(s): d m / d s_j = x_j (g_j - sum_k x_k g_k)
             // The installed torch (2.10, ATen cosine_similarity) clamps the two norms IN PLACE under no-grad: the VALUE uses
@@ -432,6 +487,18 @@ risk_matrix_kernel(const float *__restrict__ ref, const float *__restrict__ x0, 
                 for (int j = tid; j < S; j += kMatThreads) jac[(size_t)b * S + j] = (float)grad(j);
             }
         }
+    }
+}
+
+// d loss / d x0 of a risk loss whose matrix came from risk_matrix_kernel: ds[b][j] = jac[b][j] * dmat[b][0] (the column-0 entry of
+// the tail's gradient, read at a row stride so that a rank's rows of an all-gathered matrix are used in place).
+__global__ void __launch_bounds__(256)
+risk_scores_grad_kernel(const float *__restrict__ jac, const float *__restrict__ coef, int coef_stride, long long B, int S,
+                        float *__restrict__ ds) {
+    const long long n = B * (long long)S;
+    for (long long e = ltr_block_id() * 256 + threadIdx.x; e < n; e += 256ll * gridDim.x * gridDim.y) {
+        const long long b = e / S;
+        ds[e] = jac[e] * coef[b * coef_stride];
     }
 }
 
@@ -464,8 +531,8 @@ int ltr_trisk_fwd_bwd(const float *model, const float *baseline, int Q, float al
 int ltr_trisk_tail_fwd_bwd(const float *mat, int Q, float alpha, int flip, float factor, float *value, float *dmat, void *stream) {
     if (!mat || !value) return LTR_ERR_NULL;
     if (Q < 1 || Q > (1 << 29)) return LTR_ERR_SHAPE;
-    hipLaunchKernelGGL(trisk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, mat, Q, alpha, flip ? 1 : 0, factor, value,
-                       dmat);
+    hipLaunchKernelGGL(trisk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, mat, 1, Q, 0, alpha, flip ? 1 : 0, factor,
+                       value, dmat);
     return status();
 }
 
@@ -474,10 +541,63 @@ int ltr_risk_tail_fwd_bwd(const float *mat, int Q, int n_systems, float alpha, i
     if (!mat || !value) return LTR_ERR_NULL;
     if (Q < 1 || n_systems < 1 || (long long)Q * n_systems > (1ll << 30)) return LTR_ERR_SHAPE;
     if ((kind != 0 && kind != 1) || strategy < 1 || strategy > 3) return LTR_ERR_PARAM;
-    hipLaunchKernelGGL(risk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, mat, Q, n_systems, alpha, kind, strategy,
+    hipLaunchKernelGGL(risk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, mat, 1, Q, 0, n_systems, alpha, kind, strategy,
                        flip ? 1 : 0, factor, zquirk ? 1 : 0, value, dmat);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? LTR_OK : (int)e;
+}
+
+int ltr_risk_tail_blocks_fwd_bwd(const float *blocks, int n_blocks, int block_rows, int n_systems, float alpha, int kind, int strategy,
+                                 int flip, float factor, int zquirk, float *value, float *dmat, void *stream) {
+    if (!blocks || !value) return LTR_ERR_NULL;
+    if (n_blocks < 1 || n_blocks > kMaxRowBlocks || block_rows < 0 || n_systems < 1 ||
+        (long long)n_blocks * block_rows * n_systems > (1ll << 30))
+        return LTR_ERR_SHAPE;
+    if ((kind != 0 && kind != 1) || strategy < 1 || strategy > 3) return LTR_ERR_PARAM;
+    hipLaunchKernelGGL(risk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, blocks, n_blocks, block_rows, 1, n_systems,
+                       alpha, kind, strategy, flip ? 1 : 0, factor, zquirk ? 1 : 0, value, dmat);
+    return status();
+}
+
+int ltr_trisk_tail_blocks_fwd_bwd(const float *blocks, int n_blocks, int block_rows, float alpha, int flip, float factor, float *value,
+                                  float *dmat, void *stream) {
+    if (!blocks || !value) return LTR_ERR_NULL;
+    if (n_blocks < 1 || n_blocks > kMaxRowBlocks || block_rows < 0 || (long long)n_blocks * block_rows > (1 << 29)) return LTR_ERR_SHAPE;
+    hipLaunchKernelGGL(trisk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, blocks, n_blocks, block_rows, 1, alpha,
+                       flip ? 1 : 0, factor, value, dmat);
+    return status();
+}
+
+int ltr_risk_matrix_rows_fwd(const float *ref, const float *x0, const float *rest, int B, int S, int n_rest, int mode, int lt, int ideal,
+                             int ones, float *mat, float *jac, void *stream) {
+    if (!ref || !x0 || !mat || (n_rest > 0 && !rest)) return LTR_ERR_NULL;
+    if (B < 0 || S < 1 || S > kMatMaxS || n_rest < 0 || n_rest > 64) return LTR_ERR_SHAPE;
+    if (mode < 0 || mode > 2 || lt < 1 || lt > 3) return LTR_ERR_PARAM;
+    if (B == 0) return LTR_OK;
+    hipLaunchKernelGGL(risk_matrix_kernel, dim3(B), dim3(kMatThreads), (size_t)2 * S * sizeof(float), (hipStream_t)stream, ref, x0, rest, B,
+                       S, n_rest, mode, lt, ideal ? 1 : 0, ones ? 1 : 0, nullptr, 0, mat, jac);
+    return status();
+}
+
+int ltr_risk_matrix_cached_fwd(const float *ref, const float *x0, const float *cached, int cache_stride, int B, int S, int n_cached,
+                               int mode, int lt, float *mat, float *jac, void *stream) {
+    if (!ref || !x0 || !mat || (n_cached > 0 && !cached)) return LTR_ERR_NULL;
+    if (B < 0 || S < 1 || S > kMatMaxS || n_cached < 0 || n_cached > 65 || cache_stride < n_cached) return LTR_ERR_SHAPE;
+    if (mode < 0 || mode > 2 || lt < 1 || lt > 3) return LTR_ERR_PARAM;
+    if (B == 0) return LTR_OK;
+    hipLaunchKernelGGL(risk_matrix_kernel, dim3(B), dim3(kMatThreads), (size_t)2 * S * sizeof(float), (hipStream_t)stream, ref, x0,
+                       cached ? cached : x0, B, S, n_cached, mode, lt, 0, 0, cached ? cached : x0, cache_stride, mat, jac);
+    return status();
+}
+
+int ltr_risk_scores_grad(const float *jac, const float *dmat, int dmat_stride, int B, int S, float *dscores, void *stream) {
+    if (!jac || !dmat || !dscores) return LTR_ERR_NULL;
+    if (B < 0 || S < 1 || dmat_stride < 1) return LTR_ERR_SHAPE;
+    if (B == 0) return LTR_OK;
+    const long long blocks = ((long long)B * S + 255) / 256;
+    hipLaunchKernelGGL(risk_scores_grad_kernel, ltr_grid(blocks < 4096 ? blocks : 4096), dim3(256), 0, (hipStream_t)stream, jac, dmat,
+                       dmat_stride, (long long)B, S, dscores);
+    return status();
 }
 
 int ltr_risk_matrix_fwd(const float *ref, const float *x0, const float *rest, int B, int S, int n_rest, int mode, int lt, int ideal,
@@ -487,7 +607,7 @@ int ltr_risk_matrix_fwd(const float *ref, const float *x0, const float *rest, in
     if (mode < 0 || mode > 2 || lt < 1 || lt > 3) return LTR_ERR_PARAM;
     if (B == 0) return LTR_OK;
     hipLaunchKernelGGL(risk_matrix_kernel, dim3(B), dim3(kMatThreads), (size_t)2 * S * sizeof(float), (hipStream_t)stream, ref, x0, rest, B,
-                       S, n_rest, mode, lt, ideal ? 1 : 0, mat, jac);
+                       S, n_rest, mode, lt, ideal ? 1 : 0, 0, nullptr, 0, mat, jac);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? LTR_OK : (int)e;
 }

@@ -38,6 +38,15 @@ _PROTOTYPES = {
                                       P, P, P]),
     "ltr_lambda_colsum_sys_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, P, P]),
     "ltr_lambda_colsum_sys_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, P, P, P]),
+    "ltr_lambda_colsum_sys_bwd_coef": (c_int, [P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, P, P, c_int,
+                                               P, P]),
+    "ltr_lambda_risk_model_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
+                                          c_int, P, P, P]),
+    "ltr_risk_matrix_rows_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "ltr_risk_matrix_cached_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "ltr_risk_scores_grad": (c_int, [P, P, c_int, c_int, c_int, P, P]),
+    "ltr_risk_tail_blocks_fwd_bwd": (c_int, [P, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_float, c_int, P, P, P]),
+    "ltr_trisk_tail_blocks_fwd_bwd": (c_int, [P, c_int, c_int, c_float, c_int, c_float, P, P, P]),
     "ltr_risk_fwd_bwd": (c_int, [P, c_int, c_int, c_int, c_float, c_int, P, P, P]),
     "ltr_trisk_fwd_bwd": (c_int, [P, P, c_int, c_float, P, P, P, P]),
     "ltr_trisk_tail_fwd_bwd": (c_int, [P, c_int, c_float, c_int, c_float, P, P, P]),

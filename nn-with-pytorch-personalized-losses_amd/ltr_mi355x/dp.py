@@ -8,6 +8,12 @@ approxNDCG is a MEAN over the global batch -> each rank pre-scales by 1/B_global
 local batch size rides along in the buffer and the division follows the all-reduce; ListNet / lambdaLoss("sum") are
 SUMs -> no scaling; lambdaLoss("mean") divides by the GLOBAL kept-pair count, all-reduced in the same buffer.
 Works unchanged on the gloo backend (CPU tests, world_size 2).
+
+The risk-sensitive losses (geoRisk / zRisk / tRisk, Listnet and Lambda forms) are NOT sums over queries: the flip's whole-matrix
+maximum, the column sums, the total and tRisk's mean / std are batch-wide.  Through ModuleShardedTrainer each rank computes the risk
+of its own shard and the gradients are added -- that is not the global-batch loss, and not its gradient.  QueryShardedTrainer with a
+risk FusedRanker trains them correctly: one all_gather of the [queries, systems] matrix rows, the tail on the whole matrix on every
+rank (ltr_mi355x.risk_step), then the usual one all-reduce of [grads | loss].
 """
 import torch
 import torch.distributed as dist
@@ -63,6 +69,9 @@ class QueryShardedTrainer:
         # without a per-rank salt document i of every shard would share one mask (ltr_scorer.hip keep_word)
         if hasattr(self.local, "seed_salt"):
             self.local.seed_salt = self.rank
+        # a risk-loss ranker gathers its effectiveness-matrix rows over the same group inside its step
+        if hasattr(self.local, "risk_group"):
+            self.local.risk_group, self.local.risk_rank, self.local.risk_world = group, self.rank, self.world_size
 
     def global_batch_of(self, b_local, device):
         """Sum of the ranks' local batch sizes (one 8-byte all-reduce + host read): only for local steps WITHOUT the
@@ -73,15 +82,17 @@ class QueryShardedTrainer:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
         return int(t.item())
 
-    def step(self, X, y, global_batch=None):
+    def step(self, X, y, global_batch=None, **extras):
         """One optimizer step on this rank's slates.  Returns the GLOBAL loss (0-dim tensor, no host sync).
         global_batch: total slates over all ranks this step when the caller knows it (equal shards: bench.py) -- the
         batch-mean loss is then pre-scaled inside the launch.  Default: deferred normalisation (see the class docstring);
-        every rank must make the same choice."""
+        every rank must make the same choice.  extras: per-batch inputs of the local step, passed through (a risk loss's
+        y_base= or base_cols=, sharded like X).  A risk loss has no normaliser and is not pre-scaled in either branch; with
+        global_batch its ragged-shard gather needs no host read."""
         data_dependent = getattr(self.local, "mean_kind", None) == "pairs"
         ev = self.comm_events                   # optional (start, end) torch.cuda.Event pair around the collective (bench.py)
         if self.deferred and (global_batch is None or data_dependent):
-            self.local.step(X, y, defer_norm=True)
+            self.local.step(X, y, defer_norm=True, **extras)
             if self.collective:
                 if ev is not None:
                     ev[0].record()
@@ -91,7 +102,7 @@ class QueryShardedTrainer:
             self.local.finish_norm()
         else:
             gb = int(global_batch) if global_batch else self.global_batch_of(int(X.shape[0]), X.device)
-            self.local.step(X, y, world_batch=gb)
+            self.local.step(X, y, world_batch=gb, **extras)
             if self.collective:
                 if ev is not None:
                     ev[0].record()
@@ -107,7 +118,10 @@ class ModuleShardedTrainer:
     architeture/multiLayer.py): every rank runs forward + loss + backward on its slates, then ONE all-reduce(SUM) of the
     flattened gradients (+ the loss) and the optimizer step.  `reduction`: "mean" (approxNDCG: each rank's gradient is
     weighted by B_local / B_global first) or "sum" (ListNet, lambdaLoss with reduction="sum").  Every rank gets its own
-    dropout streams (module.ltr_seed is offset by the rank)."""
+    dropout streams (module.ltr_seed is offset by the rank).
+
+    Not for the risk-sensitive losses: a risk value is batch-coupled, so the sum of per-shard risks (and of their gradients) is not
+    the global-batch loss.  Train those with QueryShardedTrainer and a risk FusedRanker (see the module docstring)."""
 
     def __init__(self, module, optimizer, reduction="mean", group=None):
         if reduction not in ("mean", "sum"):

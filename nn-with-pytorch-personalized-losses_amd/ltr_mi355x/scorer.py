@@ -34,7 +34,7 @@ def net_id(kind, n_features):
     if n_features < 1:
         raise ValueError(f"input_size must be positive, got {n_features}")
     return COMPILED_FEATURES[64 if n_features <= 64 else 136][which] | (n_features << 8)
-LOSS_APPROXNDCG, LOSS_LISTNET, LOSS_LAMBDA = 0, 1, 2
+LOSS_APPROXNDCG, LOSS_LISTNET, LOSS_LAMBDA, LOSS_RISK = 0, 1, 2, 3
 _MASK64 = (1 << 64) - 1
 
 
@@ -315,9 +315,15 @@ class FusedRanker:
     (main_batch_execution.py:128-170), with X read from HBM once and nothing but the loss written back.
     `flat_grad` is a single fp32 buffer that every `param.grad` aliases: one all-reduce for data parallel.
     `grad_div` rescales the mean-type losses for a global batch (B_global = B * world_size).
+
+    The six risk-sensitive losses (loss="geoRiskLambdaLoss", ..., with the reference's keyword arguments in `risk_args`; `alpha` stays
+    approxNDCG's) take their baselines per step: `step(X, y, y_base=...)` or the cached `step(X, y, base_cols=baseline_columns(y,
+    y_base))` -- see ltr_mi355x.risk_step.
     """
 
     LOSSES = {"approxNDCG": LOSS_APPROXNDCG, "listnet": LOSS_LISTNET, "lambdaLoss": LOSS_LAMBDA}
+    LOSSES.update({name: LOSS_RISK for name in ("geoRiskListnetLoss", "geoRiskLambdaLoss", "zRiskListnetLoss", "zRiskLambdaLoss",
+                                                  "tRiskListnetLoss", "tRiskLambdaLoss")})
 
     def __new__(cls, module, *args, **kwargs):
         # an FC-only make_model LTRModel (architeture/multiLayer.py) runs folded into one scoring vector: ltr_mi355x.linear
@@ -328,9 +334,18 @@ class FusedRanker:
 
     def __init__(self, module, loss="approxNDCG", alpha=1.0, eps=1e-10, padded_value_indicator=-1,
                  apply_sigmoid=False, grid=None, weighing_scheme=None, k=None, sigma=1.0, mu=10.0,
-                 reduction="sum", reduction_log="binary"):
+                 reduction="sum", reduction_log="binary", risk_args=None):
         if loss not in self.LOSSES:
             raise KeyError(f"fused loss must be one of {sorted(self.LOSSES)}, got {loss!r}")
+        self.risk = None
+        if self.LOSSES[loss] == LOSS_RISK:
+            from .risk_step import RiskSpec
+            self.risk = RiskSpec(loss, risk_args)
+            # data parallel: ltr_mi355x.dp.QueryShardedTrainer sets (group, rank, world) -- the risk step all-gathers its matrix rows
+            self.risk_group = None
+            self.risk_rank, self.risk_world = 0, 1
+        elif risk_args is not None:
+            raise TypeError(f"risk_args belongs to the risk-sensitive losses, not {loss!r}")
         self.module = module
         if module._ltr_net == NET_WIDE:
             raise NotImplementedError("the fused step is built for scorers of up to 136 input features; wider networks run as "
@@ -428,11 +443,13 @@ class FusedRanker:
         self.flat_grad.div_(torch.where(n > 0, n, torch.ones_like(n)))
         self.flat[self.info.n_params:].div_(n)
 
-    def step(self, X, y, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False):
+    def step(self, X, y, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False, y_base=None, base_cols=None):
         """Run the fused pass on this rank's slates.  Returns the 0-dim LOCAL loss contribution, already
         scaled for the global batch (sum over ranks == the reference's loss on the global batch).
         defer_norm=True: leave SUM-form contributions in `flat` and this rank's normaliser in `flat_ext[-1]`; the caller
-        all-reduces `flat_ext` and calls `finish_norm()` (ltr_mi355x.dp.QueryShardedTrainer)."""
+        all-reduces `flat_ext` and calls `finish_norm()` (ltr_mi355x.dp.QueryShardedTrainer).
+        Risk losses: y_base [B, S, n] ([B, S] for tRisk) or base_cols (baseline_columns) -- one of them is required.  Under data
+        parallel their loss is the GLOBAL value (on rank 0; 0 elsewhere, so the all-reduced slot holds it once)."""
         info = self.info
         require_device(X, y)
         if X.dim() != 3 or X.shape[2] != info.F or tuple(y.shape[:2]) != tuple(X.shape[:2]):
@@ -440,6 +457,11 @@ class FusedRanker:
         B, S = int(X.shape[0]), int(X.shape[1])
         if S < 1 or S > 2048:
             raise ValueError(f"slate_length {S} outside the supported range 1..2048")
+        risk_in = None
+        if self.risk is not None:
+            risk_in = self._risk_inputs(B, S, y_base, base_cols)
+        elif y_base is not None or base_cols is not None:
+            raise TypeError(f"y_base / base_cols belong to the risk-sensitive losses, not {self.loss!r}")
         lambda_mean = self.loss_kind == LOSS_LAMBDA and self.reduction == "mean"
         if lambda_mean and not defer_norm and world_batch not in (None, B):
             raise ValueError('lambdaLoss reduction="mean" divides by the GLOBAL kept-pair count, which no rank knows before '
@@ -447,7 +469,7 @@ class FusedRanker:
         # one launch when the slate tiles a 128-document super-tile; otherwise forward launch + loss kernel +
         # backward launch -- same flat gradient buffer either way
         one_launch = S in (32, 64, 128)       # (and the reference's dropout probability: see below)
-        if B == 0:
+        if B == 0 and self.risk is None:
             # no slates on this rank: zero gradient contribution; the loss of an empty batch is what the
             # reference's reduction gives (mean of nothing = nan, sum of nothing = 0) unless a global batch is set
             self.flat_ext.zero_()
@@ -481,7 +503,7 @@ class FusedRanker:
             if self._slate is None or self._slate.numel() < B:
                 self._slate = torch.empty(B, dtype=torch.float32, device=self.device)
             h = lib()
-            three = not one_launch or (dropout > 1 and k1 is None)     # p != 0.5: only the forward kernels carry that stream
+            three = not one_launch or (dropout > 1 and k1 is None) or self.risk is not None  # p != 0.5: only the forward kernels carry that stream
             fold = (self.fold32 if three else self.fold) if (k1 is None and k2 is None) else None
             net, packed, partials, grid = self.net, self.packed, self.partials, self.grid
             pf = None
@@ -494,6 +516,11 @@ class FusedRanker:
                 packed = self.fold_packed[:fold.packed_floats]
                 pack_params(fold.handle, fw + [pf[5]], out=packed)
                 net, partials, grid = fold.net, self.fold_partials, (self.grid if three else self.fold_grid)
+            if self.risk is not None:
+                out = self._step_risk(h, x2, yy, B, S, dropout, int(seed) & _MASK64, k1, k2, risk_in, world_batch, fold, pf, net, packed,
+                                      partials)
+                self._bind_grads()
+                return out
             if three:
                 out = self._step_three_launches(h, x2, yy, B, S, dropout, int(seed) & _MASK64, k1, k2, scale, lambda_mean,
                                                 defer_norm, fold, pf, net, packed, partials)
@@ -579,4 +606,105 @@ class FusedRanker:
             torch.sum(count, dim=0, keepdim=True, out=self._norm)
             if not defer_norm:
                 self._divide_by_norm()
+        return self._loss_out
+
+    # ------------------------------------------------------------------------------------------ risk-sensitive losses
+    def _risk_inputs(self, B, S, y_base, base_cols):
+        """Host checks of a risk step's per-batch extras -> (yb [B, S, nb] or None, cache [B, C] or None, n_const)."""
+        R = self.risk
+        if (y_base is None) == (base_cols is None):
+            raise ValueError(f"{R.name}: pass exactly one of y_base= and base_cols=")
+        if not 2 <= S <= 2048:
+            raise NotImplementedError(f"{R.name}: the fused step takes slates of 2..2048 documents, got {S}")
+        if self.risk_world <= 1 and B < 2:
+            raise NotImplementedError(f"{R.name}: the fused step takes batches of at least 2 queries, got {B}")
+        if base_cols is not None:
+            require_device(base_cols)
+            bc, n_c = R.cached(B, S, base_cols)
+            return None, bc, n_c
+        require_device(y_base)
+        yb = R.baselines(B, S, y_base)
+        return yb, None, R.n_const(yb.shape[2])
+
+    def baseline_columns(self, y, y_base):
+        """The constant part of a risk loss's matrix for these queries: [Q, C] fp32, aligned with y's queries (index / shuffle it with X
+        and y), to pass as step(..., base_cols=...).  Baselines' and ideal ranking's entries; for the Lambda forms also the ideal
+        ranking's column sums, so that a step runs the pair work of the model alone."""
+        from . import risk_step
+        if self.risk is None:
+            raise TypeError(f"baseline_columns belongs to the risk-sensitive losses, not {self.loss!r}")
+        require_device(y, y_base)
+        if y.dim() != 2:
+            raise ValueError(f"expected y [Q, S], got {tuple(y.shape)}")
+        Q, S = int(y.shape[0]), int(y.shape[1])
+        if not 2 <= S <= 2048:
+            raise NotImplementedError(f"{self.risk.name}: the fused step takes slates of 2..2048 documents, got {S}")
+        with torch.cuda.device(y.device):
+            yy = y.detach().to(torch.float32).contiguous()
+            return risk_step.baseline_columns(self.risk, yy, self.risk.baselines(Q, S, y_base))
+
+    def _step_risk(self, h, x2, yy, B, S, dropout, seed, k1, k2, risk_in, world_batch, fold, pf, net, packed, partials):
+        """Scorer forward (activations saved) -> matrix rows + Jacobian -> [all_gather] -> tail -> scores gradient -> scorer backward
+        -> reduce (ltr_mi355x.risk_step)."""
+        import torch.distributed as dist
+        from . import risk_step as RS
+        R = self.risk
+        yb, cache, n_c = risk_in
+        nsys = 1 + n_c
+        dev = self.device
+        n = B * S
+        world, rank = self.risk_world, self.risk_rank
+        dp = world > 1
+        if dp:
+            # every rank's rows, padded to the largest shard, behind one float holding the row count
+            if world_batch:
+                bmax = -(-int(world_batch) // world)
+            else:                                     # one size exchange (as QueryShardedTrainer.global_batch_of)
+                t = torch.tensor([B], dtype=torch.int64, device=dev)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.risk_group)
+                bmax = int(t.item())
+            if B > bmax:
+                raise ValueError(f"{R.name}: this rank holds {B} queries, more than ceil(global batch / world) = {bmax}: shard with "
+                                 "ltr_mi355x.dp.shard_range")
+            stride = 1 + bmax * nsys
+            send = torch.empty(stride, dtype=torch.float32, device=dev)
+            send[:1].fill_(float(B))
+            mat = send[1:1 + B * nsys].view(B, nsys)
+        else:
+            mat = torch.empty((B, nsys), dtype=torch.float32, device=dev)
+        scores = torch.empty(n, dtype=torch.float32, device=dev)
+        jac = torch.empty(n, dtype=torch.float32, device=dev)
+        if B > 0:
+            n_acts = int(h.ltr_mlp_acts_floats(net, n))
+            if self._acts is None or self._acts.numel() < n_acts:
+                self._acts = torch.empty(n_acts, dtype=torch.float32, device=dev)
+            check(h.ltr_mlp_forward_save(net, _ptr(x2), n, _ptr(packed), int(dropout), seed, _ptr(k1), _ptr(k2),
+                                         _ptr(scores), _ptr(self._acts), self.grid, _stream()), "ltr_mlp_forward_save")
+            RS.matrix(h, R, scores, yy, yb, cache, n_c, mat, jac)
+        loss_slot = self.flat[self.info.n_params:self.info.n_params + 1]
+        if dp:
+            recv = torch.empty((world, stride), dtype=torch.float32, device=dev)
+            dist.all_gather(list(recv.unbind(0)), send, group=self.risk_group)
+            drecv = torch.empty_like(recv)
+            value = loss_slot if rank == 0 else torch.empty(1, dtype=torch.float32, device=dev)
+            RS.tail_blocks(h, R, recv, world, bmax, nsys, value, drecv)
+            if rank != 0:
+                loss_slot.fill_(0.0)                  # the all-reduced loss slot holds the global value once
+            coef = drecv.data_ptr() + 4 * (rank * stride + 1)
+        else:
+            dmat = torch.empty((B, nsys), dtype=torch.float32, device=dev)
+            RS.tail(h, R, mat, B, nsys, loss_slot, dmat)
+            coef = dmat.data_ptr()
+        if B == 0:
+            self.flat_grad.zero_()
+            return self._loss_out
+        ds = torch.empty(n, dtype=torch.float32, device=dev)
+        RS.scores_grad(h, R, scores, yy, jac, coef, nsys, ds)
+        if self.kernel_events is not None:
+            self.kernel_events[0].record()
+        check(h.ltr_mlp_backward_saved(net, _ptr(x2), n, _ptr(packed), int(dropout), _ptr(self._acts), _ptr(ds),
+                                       _ptr(partials), self.grid, _stream()), "ltr_mlp_backward_saved")
+        if self.kernel_events is not None:
+            self.kernel_events[1].record()
+        self._reduce(fold, pf, partials, self.grid)
         return self._loss_out
