@@ -17,7 +17,7 @@ def test_f16x2_variant_passes_the_scorer_suite_at_the_fp32_bars():
     so = variant_path("f16x2")
     assert os.path.exists(so), f"{so} not built: __graft_entry__.build() builds it next to the default library"
     env = dict(os.environ, LTR_LIB=so)
-    tests = ["tests/test_scorer_gpu.py", "tests/test_two_layer_gpu.py", "tests/test_fused_gaps_gpu.py"]
+    tests = ["tests/test_scorer_gpu.py", "tests/test_two_layer_gpu.py", "tests/test_fused_gaps_gpu.py", "tests/test_persistent_tiles_gpu.py"]
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", *tests], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     tail = "\n".join(r.stdout.splitlines()[-15:])
