@@ -4,13 +4,17 @@ features, fp32, synthetic MSLR-WEB30K-shaped data resident in HBM (BASELINE.json
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
   python bench.py ... --dump-outputs DIR                  (also writes the last timed step's loss / gradients / parameters)
+  python bench.py ... --full                              (also the CPU baseline and the secondary lines, see below)
 
 A step = one optimizer step of the query-sharded trainer on `--batch` slates per GPU: ONE fused launch
 (scorer fwd -> approxNDCG -> scorer bwd -> weight gradients), a fixed-order gradient reduce, one all-reduce
 of the flat [grads | loss] buffer (N > 1) and a fused Adam update.  Per-GPU work is fixed as N grows (weak).
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the fused slate pipeline), timed
-with HIP events on its own stream inside the timed region; `cpu_baseline` is the oracle's op-level
-restatement of the reference's CPU path, timed on this box's host cores (rank 0, N = 1 only).
+with HIP events on its own stream inside the timed region.  A plain run stops there: set up, warm up, time the
+steps, dump, print.  Everything that takes runs of its own is behind `--full` (rank 0, N = 1 only):
+`cpu_baseline`, the oracle's op-level restatement of the reference's CPU path timed on the host's cores
+(`--no-cpu-baseline` skips it), and `secondary`, the other nets, precisions and config 5 measured by child
+processes (`--no-extras` skips them).
 """
 import argparse
 import json
@@ -225,9 +229,11 @@ def main():
     ap.add_argument("--loss", choices=["approxNDCG", "listnet", "lambdaLoss"], default="approxNDCG",
                     help="headline metric is approxNDCG; lambdaLoss uses ndcgLoss2PP_scheme (main_batch_execution.py:135)")
     ap.add_argument("--eval-mode", action="store_true", help="no dropout (default: training mode, like the reference loop)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also time the CPU baseline and the secondary lines (N = 1; a plain run measures the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (and with it the secondary lines)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements attached to the default headline line (split-precision variant, 136-64-1 net)")
+                    help="with --full: skip the secondary lines (split-precision variant, other nets, config 5)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write the loss, gradients and parameters of the last step as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
@@ -370,9 +376,9 @@ def main():
             out["config"]["workload"] = out["config"]["workload"].replace("(136-64-32-1)", "(136-64-32-1, l2.l1 folded to 136-32-1 inside the step)")
         out["per_rank"] = [{"rank": r, "ms_per_step_local": round(float(t[0]), 4), "kernel_ms": round(float(t[1]), 4),
                             "allreduce_ms": round(float(t[2]), 4)} for r, t in enumerate(per_rank)]
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.net, S)
-        if world == 1 and not a.no_extras and not a.no_cpu_baseline and a.net == "double" and a.loss == "approxNDCG" \
+        if a.full and world == 1 and not a.no_extras and not a.no_cpu_baseline and a.net == "double" and a.loss == "approxNDCG" \
                 and not os.environ.get("LTR_LIB"):
             out["secondary"] = secondary_lines(a)
         print(json.dumps(out), flush=True)

@@ -12,10 +12,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(out_dir, net):
+def _bench(out_dir, net, flags=("--no-cpu-baseline", "--no-extras")):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LTR_LIB")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--queries", "4096", "--batch", "1024",
-                        "--steps", "3", "--warmup", "1", "--net", net, "--no-cpu-baseline", "--no-extras", "--dump-outputs", out_dir],
+                        "--steps", "3", "--warmup", "1", "--net", net, *flags, "--dump-outputs", out_dir],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -50,3 +50,20 @@ def test_bench_dump_outputs_are_the_last_step_and_reproducible(tmp_path, net):
     loss = np.load(os.path.join(a, "loss.npy"))
     assert loss.shape == (1,) and round(float(loss[0]), 6) == ja["config"]["final_loss"]
     assert np.abs(np.load(os.path.join(a, f"grad.{next(iter(params))}.npy"))).max() > 0
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_is_the_headline_alone_and_full_adds_the_rest(tmp_path):
+    """A plain run prints the headline line without the CPU baseline or the secondary lines; --full adds the CPU baseline
+    (--no-extras keeps the secondary child runs out of this test) and leaves the dumped arrays of the same steps unchanged."""
+    a, b = str(tmp_path / "plain"), str(tmp_path / "full")
+    plain, full = _bench(a, "double", flags=()), _bench(b, "double", flags=("--full", "--no-extras"))
+    assert "cpu_baseline" not in plain and "secondary" not in plain
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["unit"] == "slates/s" and "secondary" not in full
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k], k
+    assert plain["config"]["final_loss"] == full["config"]["final_loss"]
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b))
+    for n in names:
+        assert np.array_equal(np.load(os.path.join(a, n)), np.load(os.path.join(b, n))), n

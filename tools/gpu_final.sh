@@ -8,7 +8,7 @@ run() { local name=$1 to=$2; shift 2; timeout -k 10 $to "$@" > $OUT/${TAG}_$name
 run tests 1000 python -m pytest tests -m gpu -q; grep -E "passed|failed" $OUT/${TAG}_tests.log | tail -1
 cp $OUT/parity_report.json $OUT/${TAG}_parity_report.json 2>/dev/null
 run smoke 300 python __graft_entry__.py smoke; tail -2 $OUT/${TAG}_smoke.log
-run bench 600 python bench.py --steps 20 --warmup 3; tail -1 $OUT/${TAG}_bench.log | cut -c1-300
+run bench 600 python bench.py --steps 20 --warmup 3 --full; tail -1 $OUT/${TAG}_bench.log | cut -c1-300
 run bench_c3 300 python bench.py --steps 10 --warmup 2 --loss lambdaLoss --slate 512 --queries 8192 --batch 8192 --no-cpu-baseline; tail -1 $OUT/${TAG}_bench_c3.log | cut -c1-200
 run bench_c1 300 python bench.py --steps 20 --warmup 3 --loss listnet --slate 32 --queries 400000 --batch 100000 --no-cpu-baseline; tail -1 $OUT/${TAG}_bench_c1.log | cut -c1-200
 run bench_l128 300 python bench.py --steps 20 --warmup 3 --loss lambdaLoss --no-cpu-baseline; tail -1 $OUT/${TAG}_bench_l128.log | cut -c1-200

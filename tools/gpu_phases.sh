@@ -11,7 +11,7 @@ for skip in 0 1; do
   LTR_DEBUG_SKIP=$skip timeout -k 10 120 python tools/bench_phases.py >> $OUT/${TAG}_phases.log 2>&1 || { echo "phase run $skip failed"; tail -3 $OUT/${TAG}_phases.log; exit 9; }
 done
 grep -h net $OUT/${TAG}_phases.log
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > $OUT/${TAG}_bench.log 2>&1; tail -1 $OUT/${TAG}_bench.log
+timeout -k 10 300 python bench.py --steps 20 --warmup 3 --full > $OUT/${TAG}_bench.log 2>&1; tail -1 $OUT/${TAG}_bench.log
 timeout -k 10 200 python bench.py --steps 20 --warmup 3 --net triple --no-cpu-baseline > $OUT/${TAG}_bench_triple.log 2>&1; tail -1 $OUT/${TAG}_bench_triple.log
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > $REPO/$OUT/${TAG}_counters.txt 2>&1

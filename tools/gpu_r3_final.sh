@@ -17,7 +17,7 @@ run smoke 300 python __graft_entry__.py smoke; tail -2 $OUT/${TAG}_smoke.log
 fi
 [ $PART = tests ] && exit 0
 if [ $PART = bench ] || [ $PART = all ]; then
-run bench 900 python bench.py --steps 20 --warmup 3; tail -1 $OUT/${TAG}_bench.log | cut -c1-300
+run bench 900 python bench.py --steps 20 --warmup 3 --full; tail -1 $OUT/${TAG}_bench.log | cut -c1-300
 for lib in fp32 f16x2; do
   if [ $lib = f16x2 ]; then export LTR_LIB=$V; else unset LTR_LIB; fi
   run bench_c3_$lib 300 python bench.py --steps 10 --warmup 2 --loss lambdaLoss --slate 512 --queries 8192 --batch 8192 --no-cpu-baseline --no-extras; tail -1 $OUT/${TAG}_bench_c3_$lib.log | cut -c1-160

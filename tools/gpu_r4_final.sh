@@ -6,7 +6,7 @@ timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $OUT/r4f_tests.log 2>&1
 echo "[tests] exit $rc: $(tail -n 1 $OUT/r4f_tests.log | cut -c1-200)"
 [ $rc -ne 0 ] && { grep -E "^E |FAILED" $OUT/r4f_tests.log | head -n 12 | cut -c1-250; exit $rc; }
 timeout -k 10 300 python __graft_entry__.py smoke 2>&1 | grep "smoke" || exit 1
-timeout -k 10 900 python bench.py > $OUT/r4f_bench_default.log 2>$OUT/r4f_bench_default.err || { tail -n 5 $OUT/r4f_bench_default.err; exit 1; }
+timeout -k 10 900 python bench.py --full > $OUT/r4f_bench_default.log 2>$OUT/r4f_bench_default.err || { tail -n 5 $OUT/r4f_bench_default.err; exit 1; }
 tail -n 1 $OUT/r4f_bench_default.log | python3 -c '
 import sys, json
 j = json.loads(sys.stdin.read())

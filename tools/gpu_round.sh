@@ -15,7 +15,7 @@ run() {  # name, timeout, cmd...
 }
 run tests 900 python -m pytest tests -m gpu -x -q; tail -25 $OUT/${TAG}_tests.log
 run smoke 300 python __graft_entry__.py smoke; tail -3 $OUT/${TAG}_smoke.log
-run bench 600 python bench.py --steps 20 --warmup 3; tail -2 $OUT/${TAG}_bench.log
+run bench 600 python bench.py --steps 20 --warmup 3 --full; tail -2 $OUT/${TAG}_bench.log
 run bench_triple 300 python bench.py --steps 20 --warmup 3 --net triple --no-cpu-baseline; tail -1 $OUT/${TAG}_bench_triple.log
 run bench_losses 300 python tools/bench_losses.py; tail -9 $OUT/${TAG}_bench_losses.log
 cd /tmp && export TMPDIR=/tmp
