@@ -29,10 +29,17 @@ int ltr_enc_cast_bf16(const float *src, uint16_t *dst, int64_t n, void *stream);
  * 64-bit word in device memory (0 after load).  The reference draws a new mask per forward from torch's generator
  * (architeture/transformer.py:30,52,161 -- nn.Dropout); a host passes a new `seed` per step for that.  A launch sequence recorded
  * into a hipGraph has its `seed` arguments frozen, so it begins with ltr_enc_seed_advance (a kernel node): each replay then uses
- * the next epoch, forward and backward of the same replay the same one.  All three are stream-ordered like any other launch;
- * ltr_enc_seed_get synchronises the device (tests). */
+ * the next epoch, forward and backward of the same replay the same one.  The epoch is read when a kernel runs, so a caller that moves
+ * it between a forward and its backward (seed_set / _advance, a replay of another captured step) would hand the backward other masks
+ * than the forward drew: a forward that draws dropout copies the epoch into an 8-byte device word `slot` of its own
+ * (ltr_enc_seed_save), and its backward calls ltr_enc_seed_swap(slot) before its first dropout kernel and again after its last one --
+ * the backward runs at the forward's epoch and leaves the caller's in place (the slot holds the forward's again, for a second backward).
+ * All are stream-ordered like any other launch (no host synchronisation; they can be captured); ltr_enc_seed_get synchronises the
+ * device (tests). */
 int ltr_enc_seed_set(uint64_t value, void *stream);
 int ltr_enc_seed_advance(uint64_t delta, void *stream);
+int ltr_enc_seed_save(uint64_t *slot, void *stream);
+int ltr_enc_seed_swap(uint64_t *slot, void *stream);
 int ltr_enc_seed_get(uint64_t *value);
 
 /* out[i] = 1 if element i of `stream_id` is kept (see the header comment), i in [0, n). */

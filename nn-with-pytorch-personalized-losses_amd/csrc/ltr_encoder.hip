@@ -78,6 +78,15 @@ __device__ __forceinline__ unsigned drop_key1(unsigned long long seed, int strea
     return mix32((unsigned)(drop_seed(seed) >> 32) + 0x85EBCA6Bu * (unsigned)stream_id + 0x165667B1u);
 }
 __global__ void seed_epoch_kernel(unsigned long long v, int add) { g_drop_epoch = add ? g_drop_epoch + v : v; }
+// What a forward hands its backward: the epoch its kernels drew with, copied into a device word of the caller's (save), and swapped
+// in front of the backward's first dropout kernel and back after its last one (swap), all stream-ordered: no host round trip, and
+// legal inside a graph capture.
+__global__ void seed_save_kernel(unsigned long long *dst) { *dst = g_drop_epoch; }
+__global__ void seed_swap_kernel(unsigned long long *slot) {
+    const unsigned long long v = *slot;
+    *slot = g_drop_epoch;
+    g_drop_epoch = v;
+}
 // (32-bit integer multiplies are quarter rate: the high word of the quad counter -- zero below 2^34 elements per stream, i.e. always
 // in practice -- joins the additive key between the two multiplies as (hi << 16 | hi) instead of costing a third multiply.)
 __device__ __forceinline__ unsigned drop_word(unsigned long long seed, int stream_id, unsigned long long quad) {
@@ -2080,6 +2089,16 @@ int ltr_enc_seed_set(uint64_t value, void *stream) {
 }
 int ltr_enc_seed_advance(uint64_t delta, void *stream) {
     hipLaunchKernelGGL(seed_epoch_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned long long)delta, 1);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+int ltr_enc_seed_save(uint64_t *slot, void *stream) {
+    if (!slot) return LTR_ERR_NULL;
+    hipLaunchKernelGGL(seed_save_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned long long *)slot);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+int ltr_enc_seed_swap(uint64_t *slot, void *stream) {
+    if (!slot) return LTR_ERR_NULL;
+    hipLaunchKernelGGL(seed_swap_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned long long *)slot);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 int ltr_enc_seed_get(uint64_t *value) {

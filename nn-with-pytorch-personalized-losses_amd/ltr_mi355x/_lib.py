@@ -61,6 +61,8 @@ _PROTOTYPES = {
     "ltr_enc_splitk_epilogue": (c_int, [P, c_int, c_int64, c_int, P, c_float, c_uint64, c_int, P, P, P]),
     "ltr_enc_seed_set": (c_int, [c_uint64, P]),
     "ltr_enc_seed_advance": (c_int, [c_uint64, P]),
+    "ltr_enc_seed_save": (c_int, [P, P]),
+    "ltr_enc_seed_swap": (c_int, [P, P]),
     "ltr_enc_seed_get": (c_int, [ctypes.POINTER(c_uint64)]),
     "ltr_enc_dropout_mask": (c_int, [c_uint64, c_int, c_int64, c_float, P, P]),
     "ltr_enc_attn_dropout_mask": (c_int, [c_uint64, c_int, c_int, c_int, c_int, c_float, P, P]),

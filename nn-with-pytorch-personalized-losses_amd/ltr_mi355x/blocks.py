@@ -71,6 +71,7 @@ class Features(torch.autograd.Function):
             ctx.st = None
             return torch.empty((B, S, spec.d_model), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
+            ctx.epoch = E.epoch_save(x.device) if E.draws_dropout(spec, training) else None
             st = E._run_forward(spec, x, mask, seed, training, params)
             out = st["final_x"]
             if final_norm:
@@ -80,7 +81,7 @@ class Features(torch.autograd.Function):
                 # the residual stream's last tensor stays in ctx.st for the backward (outside save_for_backward, so no version
                 # counter guards it): hand out a copy, an in-place edit of the output must not reach it
                 out = out.clone()
-        ctx.st = st
+        ctx.st = E.hand_over(ctx, st)
         return out.view(B, S, spec.d_model)
 
     @staticmethod
@@ -90,10 +91,10 @@ class Features(torch.autograd.Function):
         if ctx.st is None:
             return (None, None, torch.zeros(xshape, dtype=xdt, device=dev), None, None, None,
                     *[torch.zeros(s, dtype=t, device=dev) for s, t in zip(shapes, dts)])
-        spec, st = ctx.spec, ctx.st
+        spec, st = ctx.spec, E.take_over(ctx)
         B, S, F = st["dims"]
         T, d, prm = B * S, spec.d_model, st["prm"]
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), E.forward_epoch(ctx.epoch):
             g = dout.detach().to(torch.float32).contiguous().view(T, d)
             with E.deferred_reductions():
                 tail = []
@@ -117,27 +118,28 @@ class LayerNormFn(torch.autograd.Function):
         xf = _tokens(x, d)
         T = xf.shape[0]
         ctx.meta = (x.dtype, tuple(x.shape), a.dtype, b.dtype, float(eps), int(standard))
+        ctx.empty = T == 0
         if T == 0:
-            ctx.xf = None
             return torch.empty(x.shape, dtype=torch.float32, device=x.device)
         af, bf = _f32(a), _f32(b)
         with torch.cuda.device(x.device):
             _, y = E.layernorm_fwd(xf, af, bf, T, d, eps, standard, want_f32=True)
-        ctx.xf, ctx.af = xf, af
+        ctx.save_for_backward(xf, af)           # fp32 contiguous x / a: the caller's own tensors (version-checked at unpack)
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
         xdt, xshape, adt, bdt, eps, standard = ctx.meta
         d = xshape[-1]
-        if ctx.xf is None:
+        if ctx.empty:
             z = torch.zeros(d, device=dy.device)
             return torch.zeros(xshape, dtype=xdt, device=dy.device), z.to(adt), z.to(bdt), None, None
-        T = ctx.xf.shape[0]
+        xf, af = ctx.saved_tensors
+        T = xf.shape[0]
         with torch.cuda.device(dy.device):
             g = dy.detach().to(torch.float32).contiguous().view(T, d)
             dx = torch.zeros((T, d), dtype=torch.float32, device=dy.device)
-            ga, gb = E.layernorm_bwd(ctx.xf, ctx.af, g, T, d, eps, standard, dx)
+            ga, gb = E.layernorm_bwd(xf, af, g, T, d, eps, standard, dx)
         return dx.view(xshape).to(xdt), ga.to(adt), gb.to(bdt), None, None
 
 
@@ -211,28 +213,29 @@ class ScoreLinearFn(torch.autograd.Function):
         T = xf.shape[0]
         ctx.meta = (x.dtype, tuple(x.shape), W.dtype, b.dtype, d)
         out = torch.empty(T, dtype=torch.float32, device=x.device)
-        ctx.xf = None
+        ctx.empty = T == 0
         if T:
             wf, bf = _f32(W), _f32(b)
             with torch.cuda.device(x.device):
                 check(lib().ltr_enc_score_fwd(_ptr(xf), None, None, _ptr(wf), _ptr(bf), T, d, E.LN_EPS, 0, _ptr(out), _stream()),
                       "ltr_enc_score_fwd")
-            ctx.xf, ctx.wf = xf, wf
+            ctx.save_for_backward(xf, wf)       # fp32 contiguous x / W: the caller's own tensors (version-checked at unpack)
         return out.view(*x.shape[:-1], 1)
 
     @staticmethod
     def backward(ctx, dscores):
         xdt, xshape, wdt, bdt, d = ctx.meta
         dev = dscores.device
-        if ctx.xf is None:
+        if ctx.empty:
             return torch.zeros(xshape, dtype=xdt, device=dev), torch.zeros((1, d), dtype=wdt, device=dev), torch.zeros(1, dtype=bdt, device=dev)
-        T = ctx.xf.shape[0]
+        xf, wf = ctx.saved_tensors
+        T = xf.shape[0]
         with torch.cuda.device(dev):
             ds = dscores.detach().to(torch.float32).contiguous().view(T)
             nblk = max(1, min(E._NBLK, (T + 3) // 4))
             dx = torch.empty((T, d), dtype=torch.float32, device=dev)
             parts = torch.empty((nblk, 3 * d + 8), dtype=torch.float32, device=dev)
-            check(lib().ltr_enc_score_bwd(_ptr(ctx.xf), None, None, _ptr(ctx.wf), _ptr(ds), T, d, E.LN_EPS, 0, _ptr(dx), _ptr(parts), nblk,
+            check(lib().ltr_enc_score_bwd(_ptr(xf), None, None, _ptr(wf), _ptr(ds), T, d, E.LN_EPS, 0, _ptr(dx), _ptr(parts), nblk,
                                           _stream()), "ltr_enc_score_bwd")
             g = E.sum_partials(parts, nblk, 3 * d + 8)
         return dx.view(xshape).to(xdt), g[2 * d:3 * d].view(1, d).to(wdt), g[3 * d:3 * d + 1].to(bdt)
@@ -261,6 +264,7 @@ class MultiHeadFn(torch.autograd.Function):
             ctx.saved = None
             return torch.empty((B, S, d), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
+            ctx.epoch = E.epoch_save(dev) if p > 0 else None
             srcs = [E.cast_bf16(_tokens(query, d))]
             if not same:
                 srcs += [E.cast_bf16(_tokens(key, d)), E.cast_bf16(_tokens(value, d))]
@@ -276,7 +280,8 @@ class MultiHeadFn(torch.autograd.Function):
             ctxb, lse = E.attention_fwd(qkv, mask_u8, B, S, h, dk, p, seed, 0)
             out = torch.empty((T, d), dtype=torch.float32, device=dev)
             E.gemm(ctxb, wo16, T, d, d, Cf=out, bias=_f32(bo))
-        ctx.saved = (srcs, wqkv, wo16, qkv, ctxb, mask_u8, lse)
+        ctx.saved = (srcs, wqkv, wo16, qkv, ctxb, lse)
+        ctx.save_for_backward(mask_u8)          # the caller's tensor (version-checked at unpack)
         return out.view(B, S, d)
 
     @staticmethod
@@ -288,7 +293,8 @@ class MultiHeadFn(torch.autograd.Function):
             gp = [z(d, d), z(d)] * 4
             return (None, None, None, None, z(B, S, d), None if same else z(B, S, d), None if same else z(B, S, d), None,
                     *[g.to(t) for g, t in zip(gp, p_dts)])
-        srcs, wqkv, wo16, qkv, ctxb, mask_u8, lse = ctx.saved
+        srcs, wqkv, wo16, qkv, ctxb, lse = ctx.saved
+        (mask_u8,) = ctx.saved_tensors
         T, dk = B * S, d // h
         with torch.cuda.device(dev):
             g = dout.detach().to(torch.float32).contiguous().view(T, d)
@@ -296,7 +302,8 @@ class MultiHeadFn(torch.autograd.Function):
             gWo = E._weight_grad(dy16, ctxb, T, d, d)
             dctx = torch.empty((T, d), dtype=_U16, device=dev)
             E.gemm(dy16, wo16, T, d, d, b_kmajor=True, Cb=dctx)
-            dqkv = E.attention_bwd(qkv, ctxb, dctx, lse, mask_u8, B, S, h, dk, p, seed, 0)
+            with E.forward_epoch(ctx.epoch):
+                dqkv = E.attention_bwd(qkv, ctxb, dctx, lse, mask_u8, B, S, h, dk, p, seed, 0)
             gbqkv = E._colsum(dqkv, T, 3 * d)
             need = ctx.needs_input_grad[4:7]
             if same:
@@ -335,20 +342,24 @@ class AttentionCoreFn(torch.autograd.Function):
         _mult8(d)
         ctx.meta = (B, h, S, dk, float(p), int(seed), [t.dtype for t in (query, key, value)])
         with torch.cuda.device(dev):
+            ctx.epoch = E.epoch_save(dev) if p > 0 else None
             packed = torch.cat([t.detach().to(torch.float32).transpose(1, 2).reshape(T, d) for t in (query, key, value)], 1).contiguous()
             qkv = E.cast_bf16(packed)
             ctxb, lse = E.attention_fwd(qkv, mask_u8, B, S, h, dk, p, seed, 0)
-        ctx.saved = (qkv, ctxb, mask_u8, lse)
+        ctx.saved = (qkv, ctxb, lse)
+        ctx.save_for_backward(mask_u8)          # the caller's tensor (version-checked at unpack)
         return ctxb.view(torch.bfloat16).to(torch.float32).view(B, S, h, dk).transpose(1, 2).contiguous()
 
     @staticmethod
     def backward(ctx, dout):
         B, h, S, dk, p, seed, dts = ctx.meta
-        qkv, ctxb, mask_u8, lse = ctx.saved
+        qkv, ctxb, lse = ctx.saved
+        (mask_u8,) = ctx.saved_tensors
         d, T, dev = h * dk, B * S, dout.device
         with torch.cuda.device(dev):
             dctx = E.cast_bf16(dout.detach().to(torch.float32).transpose(1, 2).reshape(T, d))
-            dqkv = E.attention_bwd(qkv, ctxb, dctx, lse, mask_u8, B, S, h, dk, p, seed, 0)
+            with E.forward_epoch(ctx.epoch):
+                dqkv = E.attention_bwd(qkv, ctxb, dctx, lse, mask_u8, B, S, h, dk, p, seed, 0)
             g = dqkv.view(torch.bfloat16).to(torch.float32).view(B, S, 3, h, dk).permute(2, 0, 3, 1, 4)
         return g[0].to(dts[0]), g[1].to(dts[1]), g[2].to(dts[2]), None, None, None
 

@@ -112,6 +112,33 @@ def seed_advance(delta=1):
     check(lib().ltr_enc_seed_advance(int(delta) & (2 ** 64 - 1), _stream()), "ltr_enc_seed_advance")
 
 
+def epoch_save(device):
+    """The current epoch -> a new 8-byte device word (ltr_enc_seed_save, stream-ordered): what a forward that draws dropout hands its
+    backward (`forward_epoch`)."""
+    slot = torch.empty(1, dtype=torch.int64, device=device)
+    check(lib().ltr_enc_seed_save(_ptr(slot), _stream()), "ltr_enc_seed_save")
+    return slot
+
+
+class forward_epoch:
+    """Runs its body at the epoch `slot` holds (epoch_save in the forward) and puts the caller's back at exit: ltr_enc_seed_swap on
+    the current stream at entry and at exit.  The backward then draws the forward's masks whatever moved the epoch in between; the slot
+    holds the forward's epoch again afterwards (a second backward of a retained graph).  slot None (no dropout drawn): nothing."""
+
+    def __init__(self, slot):
+        self.slot = slot
+
+    def __enter__(self):
+        if self.slot is not None:
+            check(lib().ltr_enc_seed_swap(_ptr(self.slot), _stream()), "ltr_enc_seed_swap")
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.slot is not None:
+            check(lib().ltr_enc_seed_swap(_ptr(self.slot), _stream()), "ltr_enc_seed_swap")
+        return False
+
+
 def seed_get():
     v = ctypes.c_uint64(0)
     check(lib().ltr_enc_seed_get(ctypes.byref(v)), "ltr_enc_seed_get")
@@ -412,6 +439,7 @@ class EncoderScores(torch.autograd.Function):
             ctx.shapes = [tuple(p.shape) for p in params]
             return torch.empty(x.shape[:2], dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
+            ctx.epoch = epoch_save(x.device) if draws_dropout(spec, training) else None
             st = _run_forward(spec, x, mask, seed, training, params)
             B, S, _ = st["dims"]
             prm = st["prm"]
@@ -422,7 +450,7 @@ class EncoderScores(torch.autograd.Function):
             scores = torch.empty((B, S), dtype=torch.float32, device=x.device)
             check(lib().ltr_enc_score_fwd(_ptr(st["final_x"]), _ptr(fa), _ptr(fb), _ptr(ow), _ptr(ob), B * S, spec.d_model, LN_EPS,
                                           1 if spec.has_encoder else 0, _ptr(scores), _stream()), "ltr_enc_score_fwd")
-        ctx.spec, ctx.seed, ctx.st = spec, int(seed), st
+        ctx.spec, ctx.seed, ctx.st = spec, int(seed), hand_over(ctx, st)
         return scores
 
     @staticmethod
@@ -430,11 +458,11 @@ class EncoderScores(torch.autograd.Function):
         if ctx.st is None:
             zeros = [torch.zeros(sh, dtype=dt, device=dscores.device) for sh, dt in zip(ctx.shapes, ctx.param_dtypes)]
             return (None, None, None, None, None, *zeros)
-        spec, seed, st = ctx.spec, ctx.seed, ctx.st
+        spec, seed, st = ctx.spec, ctx.seed, take_over(ctx)
         B, S, F = st["dims"]
         T, d, prm = B * S, spec.d_model, st["prm"]
         dev = dscores.device
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev), forward_epoch(ctx.epoch):
             ds = dscores.detach().to(torch.float32).contiguous().view(T)
             # ---- output layer (+ final norm)
             fa, fb = (prm[-4], prm[-3]) if spec.has_encoder else (None, None)
@@ -447,6 +475,26 @@ class EncoderScores(torch.autograd.Function):
                 grads = _with_tail(spec, _body_backward(spec, seed, st, dx)[0], sum_partials(parts, nblk, 3 * d + 8))
         out = [g if g is None else g.to(dt).reshape(p.shape) for g, dt, p in zip(grads, ctx.param_dtypes, prm)]
         return (None, None, None, None, None, *out)
+
+
+def draws_dropout(spec, training):
+    return bool(training) and (spec.fc_dropout > 0 or (spec.has_encoder and spec.enc_dropout > 0))
+
+
+def hand_over(ctx, st):
+    """The forward state `st` of _run_forward for ctx: the tensors that may alias the caller's parameters and input (st["prm"],
+    st["xin"]: fp32 contiguous tensors are their own `.to(fp32).contiguous()`) go through save_for_backward, so that an in-place
+    change of one between forward and backward raises, as for the reference's nn modules; every other tensor of st is the forward's
+    own (casts, activations).  Returns st without them."""
+    st = dict(st)
+    ctx.save_for_backward(st.pop("xin"), *st.pop("prm"))
+    return st
+
+
+def take_over(ctx):
+    """The backward's side of hand_over: st with "xin" / "prm" from ctx.saved_tensors (raises if one was modified in place)."""
+    xin, *prm = ctx.saved_tensors
+    return dict(ctx.st, xin=xin, prm=prm)
 
 
 def _with_tail(spec, body, tail):

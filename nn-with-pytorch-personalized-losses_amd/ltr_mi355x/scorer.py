@@ -177,7 +177,7 @@ class _MLPScores(torch.autograd.Function):
     def forward(ctx, x, net, dropout, seed, keep1, keep2, *params):
         info = NetInfo.get(net)
         dev = x.device
-        ctx.fold_pf = None
+        fold_pf = []
         with torch.cuda.device(dev):
             x2 = _docs(x, info)
             n = x2.shape[0]
@@ -187,7 +187,7 @@ class _MLPScores(torch.autograd.Function):
                 pf = _params_f32(params)
                 info = NetInfo.get(folded_net32(net))
                 packed = pack_params(info.handle, triple_fold(pf, 1) + [pf[5]])
-                ctx.fold_pf = pf[:3]
+                fold_pf = pf[:3]                 # W1, b1, W2 for the unfold: fp32 contiguous ones are the caller's own tensors
             else:
                 packed = pack_params(net, params)
             k1, k2 = _mask(keep1, n, info.H1, info.cH1), _mask(keep2, n, info.H2, info.cH2)
@@ -203,16 +203,16 @@ class _MLPScores(torch.autograd.Function):
             else:
                 check(lib().ltr_mlp_forward(info.net, _ptr(x2), n, _ptr(packed), int(dropout), seed, _ptr(k1), _ptr(k2),
                                             _ptr(scores), grid, _stream()), "ltr_mlp_forward")
-        ctx.save_for_backward(x2, packed, k1, k2)
+        ctx.save_for_backward(x2, packed, k1, k2, *fold_pf)     # (version-checked at unpack: an in-place change raises)
         ctx.acts = acts
         ctx.meta = (net, int(dropout), seed, grid, [p.dtype for p in params])
         return scores.view(*x.shape[:-1], 1)
 
     @staticmethod
     def backward(ctx, g):
-        x2, packed, k1, k2 = ctx.saved_tensors
+        x2, packed, k1, k2, *fold_pf = ctx.saved_tensors
         net, dropout, seed, grid, dtypes = ctx.meta
-        info = NetInfo.get(folded_net32(net) if ctx.fold_pf is not None else net)
+        info = NetInfo.get(folded_net32(net) if fold_pf else net)
         dev = x2.device
         n = x2.shape[0]
         with torch.cuda.device(dev):
@@ -226,10 +226,10 @@ class _MLPScores(torch.autograd.Function):
                 check(lib().ltr_mlp_backward(info.net, _ptr(x2), n, _ptr(packed), dropout, seed, _ptr(k1), _ptr(k2), _ptr(gs),
                                              _ptr(partials), grid, _stream()), "ltr_mlp_backward")
             reduce_grads(info, partials, grid, flat)
-            if ctx.fold_pf is not None:
+            if fold_pf:
                 info = NetInfo.get(net)
                 flat6 = torch.empty(info.n_params, dtype=torch.float32, device=dev)
-                triple_unfold(flat, 1, ctx.fold_pf, flat6)
+                triple_unfold(flat, 1, fold_pf, flat6)
                 flat = flat6
         grads, off = [], 0
         for shape, dt in zip(info.shapes, dtypes):
