@@ -200,12 +200,18 @@ __device__ __forceinline__ unsigned mix32(unsigned h) {
     return h;
 }
 
-// 32 keep bits for features [32*word, 32*word+32) of document `doc` in dropout layer `layer`.
-__device__ __forceinline__ unsigned keep_word(unsigned long long seed, int layer, long long doc, int word) {
+// 32 keep bits for features [32*word, 32*word+32) of document `doc` in dropout layer `layer`.  The first two mixing steps
+// depend on (seed, layer, doc) only: keep_prefix() is that part, shared by every word of a document (activate below).
+__device__ __forceinline__ unsigned keep_prefix(unsigned long long seed, int layer, long long doc) {
     unsigned h = (unsigned)seed ^ (0x9E3779B9u * (unsigned)(layer + 1));
     h = mix32(h ^ (unsigned)doc);
-    h = mix32(h ^ (unsigned)((unsigned long long)doc >> 32) ^ (unsigned)(seed >> 32));
-    return mix32(h + 0x27D4EB2Fu * (unsigned)(word + 1));
+    return mix32(h ^ (unsigned)((unsigned long long)doc >> 32) ^ (unsigned)(seed >> 32));
+}
+__device__ __forceinline__ unsigned keep_word_at(unsigned prefix, int word) {
+    return mix32(prefix + 0x27D4EB2Fu * (unsigned)(word + 1));
+}
+__device__ __forceinline__ unsigned keep_word(unsigned long long seed, int layer, long long doc, int word) {
+    return keep_word_at(keep_prefix(seed, layer, doc), word);
 }
 
 // Sum over the 16 lanes of a DPP row (= the 16 documents sharing one q); the total lands in lane 15 of the row.
@@ -380,25 +386,8 @@ __device__ __forceinline__ void activate(f32x4 (&h)[NMAX], int q, const PipeArgs
                                          long long doc) {
     const bool in_range = doc < a.n_docs;
     const bool drop = (ACT == ACT_RELU_DROP) && a.dropout;
-#pragma unroll
-    for (int To = 0; To < NT; ++To) {
-        unsigned kb = 0xFu;
-        if (drop) {
-            if (keep) {
-                const int n0 = 16 * To + 4 * q;
-                unsigned bytes = 0;
-                if (in_range && n0 < H) bytes = *reinterpret_cast<const unsigned *>(keep + doc * H + n0);
-                kb = ((bytes & 0xFFu) ? 1u : 0u) | ((bytes & 0xFF00u) ? 2u : 0u) | ((bytes & 0xFF0000u) ? 4u : 0u) |
-                     ((bytes & 0xFF000000u) ? 8u : 0u);
-            } else if (GENP && a.drop_thr16) {      // any p: 16 hash bits per unit (stream layer + 2, word = unit pair)
-                const unsigned w0 = keep_word(a.seed, layer + 2, doc, 8 * To + 2 * q), w1 = keep_word(a.seed, layer + 2, doc, 8 * To + 2 * q + 1);
-                kb = ((w0 & 0xffffu) >= a.drop_thr16 ? 1u : 0u) | ((w0 >> 16) >= a.drop_thr16 ? 2u : 0u) |
-                     ((w1 & 0xffffu) >= a.drop_thr16 ? 4u : 0u) | ((w1 >> 16) >= a.drop_thr16 ? 8u : 0u);
-            } else {
-                const unsigned wbits = keep_word(a.seed, layer, doc, To >> 1);
-                kb = (wbits >> (16 * (To & 1) + 4 * q)) & 0xFu;
-            }
-        }
+    // tile To; the keep bit of unit 16 To + 4 q + r is bit r of kb
+    auto act_tile = [&](int To, unsigned kb) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float v = h[To][r];
@@ -414,6 +403,31 @@ __device__ __forceinline__ void activate(f32x4 (&h)[NMAX], int q, const PipeArgs
             if (16 * To + 16 > H) v = (16 * To + 4 * q + r < H) ? v : 0.f;      // compile-time: last tile only
             h[To][r] = v;
         }
+    };
+    // The document's hash prefix is made once per layer and each 32-bit keep word once for its two tiles (keep_word per tile
+    // was three mixing steps, six v_mul_lo_u32, for every tile: hipcc shared none of it across the per-tile branches).
+    const unsigned pre = keep_prefix(a.seed, (GENP && a.drop_thr16) ? layer + 2 : layer, doc);
+    unsigned wbits = 0;
+#pragma unroll
+    for (int To = 0; To < NT; ++To) {
+        unsigned kb = 0xFu;
+        if (drop) {
+            if (keep) {
+                const int n0 = 16 * To + 4 * q;
+                unsigned bytes = 0;
+                if (in_range && n0 < H) bytes = *reinterpret_cast<const unsigned *>(keep + doc * H + n0);
+                kb = ((bytes & 0xFFu) ? 1u : 0u) | ((bytes & 0xFF00u) ? 2u : 0u) | ((bytes & 0xFF0000u) ? 4u : 0u) |
+                     ((bytes & 0xFF000000u) ? 8u : 0u);
+            } else if (GENP && a.drop_thr16) {      // any p: 16 hash bits per unit (stream layer + 2, word = unit pair)
+                const unsigned w0 = keep_word_at(pre, 8 * To + 2 * q), w1 = keep_word_at(pre, 8 * To + 2 * q + 1);
+                kb = ((w0 & 0xffffu) >= a.drop_thr16 ? 1u : 0u) | ((w0 >> 16) >= a.drop_thr16 ? 2u : 0u) |
+                     ((w1 & 0xffffu) >= a.drop_thr16 ? 4u : 0u) | ((w1 >> 16) >= a.drop_thr16 ? 8u : 0u);
+            } else {
+                if ((To & 1) == 0) wbits = keep_word_at(pre, To >> 1);
+                kb = wbits >> (16 * (To & 1) + 4 * q);
+            }
+        }
+        act_tile(To, kb);
     }
 }
 
