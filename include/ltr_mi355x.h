@@ -375,6 +375,22 @@ int ltr_linear_fused_step(int loss_kind, const float *X, const float *labels, in
                           float alpha, float eps, float pad, int apply_sigmoid, int scheme, int k, float sigma, float mu,
                           float lambda_eps, int log_base, float grad_scale, float *slate_loss, float *slate_count, float *partials,
                           int grid, void *stream);
+/* The six risk-sensitive losses on the folded network (riskLosses.py:8-49, :128-169, :247-276 behind main_batch_execution.py:93-94,
+ * :140-164 with net_structure = allrank).  Entry mat[q][0] of the effectiveness matrix depends on slate q's scores alone, so with
+ * j_d = d mat[q][0] / d s_d the slate's whole contribution to [Ghat | G_1] is c_q R_q, R_q = [sum_d j_d xhat_d | sum_d j_d], where
+ * c_q = d value / d mat[q][0] comes out of the tail (ltr_risk_tail_fwd_bwd / ltr_trisk_tail_fwd_bwd or their *_blocks_* forms).
+ *
+ * ltr_linear_risk_rows: the Listnet forms in one pass over X where ltr_linear_fused_supported(F, S) holds.  Scores from weff, then per
+ * slate the model's entry as ltr_risk_matrix_cached_fwd computes it (mode 0: geoRisk / zRisk Listnet, mode 2: tRiskListnetLoss; lt 1 / 2 / 3;
+ * fp32 elementwise, fp64 sums) into mat[q * n_systems], cached[q * cache_stride + 0 .. n_cached) copied to mat[q * n_systems + 1 ..],
+ * and R [B][F + 1].  X and weff 16-byte aligned.  B < 1, or (F, S) outside the supported set: LTR_ERR_SHAPE, nothing launched. */
+int ltr_linear_risk_rows(const float *X, const float *labels, int B, int S, int F, const float *weff, int input_norm, int mode, int lt,
+                         const float *cached, int cache_stride, int n_cached, float *mat, int n_systems, float *R, int grid,
+                         void *stream);
+/* partials [grid][F + 1] = per-workgroup sum_q dmat[q * dmat_stride] R[q] over a contiguous range of slates, in order: what
+ * ltr_linear_unfold_grads reduces.  dmat is read in place at the matrix's row stride, as ltr_risk_scores_grad reads it (the backward of
+ * riskLosses.py:8-49 / :128-169 / :247-276 through the scores, main_batch_execution.py:167-168).  F <= 1024; B < 1: LTR_ERR_SHAPE. */
+int ltr_linear_risk_combine(const float *R, const float *dmat, int dmat_stride, int B, int F, float *partials, int grid, void *stream);
 /* Workgroups of ltr_linear_fused_step / ltr_linear_grad_partials on a device with n_cus compute units (2 per CU). */
 int ltr_linear_grid(int n_cus);
 

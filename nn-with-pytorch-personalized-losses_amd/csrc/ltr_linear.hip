@@ -510,6 +510,217 @@ __global__ void __launch_bounds__(256) linear_fused_kernel(FusedArgs a) {
     if (tid == 0) out[F] = g1;
 }
 
+// ------------------------------------------------------------------------------------- risk-sensitive losses, Listnet forms
+// The risk losses' value is not a sum over slates (riskLosses.py:8-49, :128-169, :247-276 feed a batch-wide tail), but entry mat[q][0]
+// of their effectiveness matrix depends on slate q's scores alone.  With j_d = d mat[q][0] / d s_d and c_q = d value / d mat[q][0],
+//     [Ghat | G_1] = sum_q c_q R_q,      R_q = [ sum_d j_d xhat_d | sum_d j_d ]        (F + 1 floats per slate, known BEFORE the tail)
+// so X is read once: linear_risk_rows_kernel (linear_fused_kernel's tile loop) leaves mat[:, 0] and R, the tail runs on the matrix, and
+// linear_risk_combine_kernel forms the partials ltr_linear_unfold_grads reduces.
+//
+// The per-slate function restates risk_matrix_kernel modes 0 and 2 (ltr_risk.hip): the slate softmaxes, transformations 1 / 2 / 3 against
+// the labels, fp32 elementwise, fp64 sums, the per-norm cosine clamp with the gradient through the unclamped norm.  It is NOT shared with
+// that kernel: there a 256-thread workgroup strides one slate held in LDS, here 2 S threads hold one document each in registers, and
+// sharing one function would change that kernel's summation order, whose results stay bit-for-bit as they are.
+struct RiskRowsArgs {
+    const float *X, *labels, *weff, *cached;
+    int B, S, F, mode, lt, n_cached, cache_stride, nsys;
+    float *mat, *R;
+};
+
+inline size_t risk_rows_lds_bytes(int F) {
+    return ((size_t)kTile * (F + 4) + 4 * kTile) * sizeof(float) + 4 * 8 * sizeof(double);
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;   // butterfly: every lane holds the same bits
+}
+__device__ __forceinline__ float wave_max_f32(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// v[0 .. N) summed (MAX: maximised) over the wps waves of a slate group, first wave w0; every thread gets the result.  Lanes by
+// butterfly, waves in order.  All threads of the block call it.
+template <int N, bool MAX>
+__device__ __forceinline__ void slate_reduce(double (&v)[N], double *red /* [4][8] */, int w0, int wps) {
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = MAX ? (double)wave_max_f32((float)v[k]) : wave_sum_f64(v[k]);
+    if (wps == 1) return;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) red[wave * 8 + k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        double s = red[w0 * 8 + k];
+        for (int w = 1; w < wps; ++w) s = MAX ? fmax(s, red[(w0 + w) * 8 + k]) : s + red[(w0 + w) * 8 + k];
+        v[k] = s;
+    }
+}
+
+template <bool LN>
+__global__ void __launch_bounds__(256) linear_risk_rows_kernel(RiskRowsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int F = a.F, S = a.S, LD = F + 4, F4 = F >> 2, F1 = F + 1;
+    float *xs = smem;                          // [128][LD]
+    float *sc = xs + kTile * LD;               // [128] scores
+    float *jl = sc + kTile;                    // [128] d mat[q][0] / d s
+    float *mu = jl + kTile;                    // [128] row mean      (input_norm)
+    float *rs = mu + kTile;                    // [128] row 1 / std   (input_norm)
+    double *red = reinterpret_cast<double *>(rs + kTile);   // [4 waves][8]  (byte offset 512 (F + 4) + 2048: 8-byte aligned)
+    const int group = 2 * S, gpb = kTile / S, wps = group >> 6;    // S in {32, 64, 128}: 1, 2, 4 waves per slate
+    const int tid = threadIdx.x;
+    const int gid = tid / group, t = tid - gid * group, w0 = gid * wps;
+    const long long n = (long long)a.B * S;
+    const long long tiles = (n + kTile - 1) / kTile;
+    const int r = tid >> 4, l = tid & 15;      // DPP row r scores documents r, r + 16, ...
+    const int mode = a.mode, lt = a.lt;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        __syncthreads();                       // previous tile's LDS reads done
+        const long long base = tile * kTile;
+        const int nd = (int)(n - base < kTile ? n - base : kTile);
+        const float4 *src = reinterpret_cast<const float4 *>(a.X + base * F);
+        for (int q = tid; q < kTile * F4; q += 256) {
+            const int d = q / F4, c = q - d * F4;
+            const float4 v = d < nd ? src[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4 *>(xs + d * LD + 4 * c) = v;
+        }
+        __syncthreads();
+        for (int d = r; d < kTile; d += 16) {
+            const float *x = xs + d * LD;
+            if (LN) {
+                float s1 = 0.f;
+                for (int f = l; f < F; f += 16) s1 += x[f];
+                s1 += LTR_DPP(s1, LTR_DPP_XOR1);
+                s1 += LTR_DPP(s1, LTR_DPP_XOR2);
+                s1 += LTR_DPP(s1, LTR_DPP_HALF_MIRROR);
+                s1 += LTR_DPP(s1, LTR_DPP_MIRROR);
+                const float m = s1 / (float)F;
+                float s2 = 0.f, dt = 0.f;
+                for (int f = l; f < F; f += 16) {
+                    const float c = x[f] - m;
+                    s2 = fmaf(c, c, s2);
+                    dt = fmaf(c, a.weff[f], dt);
+                }
+                s2 += LTR_DPP(s2, LTR_DPP_XOR1);
+                s2 += LTR_DPP(s2, LTR_DPP_XOR2);
+                s2 += LTR_DPP(s2, LTR_DPP_HALF_MIRROR);
+                s2 += LTR_DPP(s2, LTR_DPP_MIRROR);
+                dt += LTR_DPP(dt, LTR_DPP_XOR1);
+                dt += LTR_DPP(dt, LTR_DPP_XOR2);
+                dt += LTR_DPP(dt, LTR_DPP_HALF_MIRROR);
+                dt += LTR_DPP(dt, LTR_DPP_MIRROR);
+                const float rstd = 1.f / sqrtf(s2 / (float)F + kLnEps);
+                if (l == 0) {
+                    sc[d] = fmaf(rstd, dt, a.weff[F]);
+                    mu[d] = m;
+                    rs[d] = rstd;
+                }
+            } else {
+                float dt = 0.f;
+                for (int c = l; c < F4; c += 16) {
+                    const float4 v = *reinterpret_cast<const float4 *>(x + 4 * c);
+                    const float4 w = reinterpret_cast<const float4 *>(a.weff)[c];
+                    dt = fmaf(v.x, w.x, dt);
+                    dt = fmaf(v.y, w.y, dt);
+                    dt = fmaf(v.z, w.z, dt);
+                    dt = fmaf(v.w, w.w, dt);
+                }
+                dt += LTR_DPP(dt, LTR_DPP_XOR1);
+                dt += LTR_DPP(dt, LTR_DPP_XOR2);
+                dt += LTR_DPP(dt, LTR_DPP_HALF_MIRROR);
+                dt += LTR_DPP(dt, LTR_DPP_MIRROR);
+                if (l == 0) sc[d] = dt + a.weff[F];
+            }
+        }
+        __syncthreads();
+        // slate b = tile * gpb + gid: documents [gid * S, gid * S + S) of the tile, document t held by thread t of the group (t < S)
+        const long long slate = tile * gpb + gid;
+        const bool active = slate < a.B, own = active && t < S;
+        if (active)                            // the constant systems' entries, copied next to the model's
+            for (int k = t; k < a.n_cached; k += group) a.mat[slate * a.nsys + 1 + k] = a.cached[slate * a.cache_stride + k];
+        const float yl = own ? a.labels[slate * S + t] : 0.f, sv = own ? sc[gid * S + t] : 0.f;
+        double mx[2] = {own ? (double)yl : -INFINITY, own ? (double)sv : -INFINITY};
+        slate_reduce<2, true>(mx, red, w0, wps);
+        const float et = own ? expf(yl - (float)mx[0]) : 0.f, ex = own ? expf(sv - (float)mx[1]) : 0.f;
+        double z[2] = {(double)et, (double)ex};
+        slate_reduce<2, false>(z, red, w0, wps);
+        const float tj = active ? et * (float)(1.0 / z[0]) : 0.f, xj = active ? ex * (float)(1.0 / z[1]) : 0.f;   // the two softmaxes
+        const float df = tj * xj - tj * tj, u = tj * tj, v = tj * xj;
+        double sm[7] = {(double)tj * tj, (double)tj * xj, (double)xj * xj, (double)df * df, (double)u * v, (double)u * u, (double)v * v};
+        slate_reduce<7, false>(sm, red, w0, wps);
+        const double nt = sm[0], aa = sm[1], nx = sm[2], cc = sm[3];
+        // cosine operands (u, v) = (t, x) [mode 0] or the products (t^2, t x) [mode 2, riskLosses.py:256-258]; nn.CosineSimilarity clamps
+        // EACH norm at eps = 1e-8 for the value while the gradient flows through the unclamped norm (risk_matrix_kernel)
+        const double ca = mode == 2 ? sm[4] : aa, cnu = mode == 2 ? sm[5] : nt, cnv = mode == 2 ? sm[6] : nx;
+        const double nrm_u = sqrt(cnu), nrm_v = sqrt(cnv);
+        const double den = (nrm_u > 1e-8 ? nrm_u : 1e-8) * (nrm_v > 1e-8 ? nrm_v : 1e-8);
+        double m;
+        if (lt == 1) m = cc;
+        else if (lt == 2) m = active ? ca / den : 0.0;
+        else m = (aa - nt) * (aa - nt);
+        const double nv_c = nrm_v > 1e-8 ? nrm_v : 1e-8;
+        const double inv_vv = nrm_v > 0.0 ? 1.0 / (nv_c * nrm_v) : 0.0;
+        double g;                              // d m / d x_j
+        {
+            const double td = tj, xd = xj;
+            if (lt == 1) g = 2.0 * td * (td * xd - td * td);
+            else if (lt == 2) {
+                const double uu = mode == 2 ? td * td : td, vv = mode == 2 ? td * xd : xd, ww = mode == 2 ? td : 1.0;
+                g = ww * (uu / den - m * vv * inv_vv);
+            } else g = 2.0 * (aa - nt) * td;
+        }
+        double dot[1] = {own ? (double)xj * g : 0.0};
+        slate_reduce<1, false>(dot, red, w0, wps);
+        // x = softmax(s): d m / d s_j = x_j (g_j - sum_k x_k g_k)
+        if (t < S) jl[gid * S + t] = own ? (float)((double)xj * (g - dot[0])) : 0.f;
+        if (active && t == 0) a.mat[slate * a.nsys] = (float)m;
+        __syncthreads();
+        // R_q = [sum_d j_d xhat_d | sum_d j_d] from the same LDS rows, thread f owning feature f, documents in order
+        if (tid < F) {
+            for (int gq = 0; gq < gpb; ++gq) {
+                const long long q = tile * gpb + gq;
+                if (q >= a.B) break;
+                float acc = 0.f, g1 = 0.f;
+                const int d0 = gq * S;
+                if (LN) {
+                    for (int d = d0; d < d0 + S; ++d) {
+                        acc = fmaf(jl[d] * rs[d], xs[d * LD + tid] - mu[d], acc);
+                        g1 += jl[d];
+                    }
+                } else {
+                    for (int d = d0; d < d0 + S; ++d) {
+                        acc = fmaf(jl[d], xs[d * LD + tid], acc);
+                        g1 += jl[d];
+                    }
+                }
+                a.R[q * F1 + tid] = acc;
+                if (tid == 0) a.R[q * F1 + F] = g1;
+            }
+        }
+    }
+}
+
+// partials[g] = sum_{q in range(g)} c_q R_q, c_q = dmat[q * dmat_stride]; workgroup g takes a contiguous range of slates, thread f
+// column f, slates in order.  Every workgroup writes its row (zeros for an empty range): the unfold reduces all `grid` rows.
+__global__ void __launch_bounds__(256) linear_risk_combine_kernel(const float *__restrict__ R, const float *__restrict__ dmat,
+                                                                  int dmat_stride, int B, int F1, float *__restrict__ partials) {
+    const int per = (B + (int)gridDim.x - 1) / (int)gridDim.x;
+    const long long q0 = (long long)blockIdx.x * per;
+    const long long q1 = q0 + per < B ? q0 + per : B;
+    for (int f = threadIdx.x; f < F1; f += 256) {
+        float acc = 0.f;
+        for (long long q = q0; q < q1; ++q) acc = fmaf(dmat[q * dmat_stride], R[q * F1 + f], acc);
+        partials[(size_t)blockIdx.x * F1 + f] = acc;
+    }
+}
+
 template <class K>
 int set_lds(K kernel, size_t lds) {
     if (lds <= 64 * 1024) return LTR_OK;
@@ -650,6 +861,54 @@ int ltr_linear_fused_step(int loss_kind, const float *X, const float *labels, in
         case 6: return launch_fused_ln<2, 6>(a, input_norm, grid, s);
         default: return launch_fused_ln<2, 7>(a, input_norm, grid, s);
     }
+}
+
+int ltr_linear_risk_rows(const float *X, const float *labels, int B, int S, int F, const float *weff, int input_norm, int mode, int lt,
+                         const float *cached, int cache_stride, int n_cached, float *mat, int n_systems, float *R, int grid,
+                         void *stream) {
+    if (!X || !labels || !weff || !mat || !R || (n_cached > 0 && !cached)) return LTR_ERR_NULL;
+    if (B < 1 || !ltr_linear_fused_supported(F, S) || n_cached < 0 || n_cached > 65 || cache_stride < n_cached ||
+        n_systems < 1 + n_cached)
+        return LTR_ERR_SHAPE;
+    if ((uintptr_t)X % 16 || (uintptr_t)weff % 16) return LTR_ERR_ALIGN;
+    if ((mode != 0 && mode != 2) || lt < 1 || lt > 3 || grid < 1 || grid > LTR_GRID_X_MAX || (input_norm != 0 && input_norm != 1))
+        return LTR_ERR_PARAM;
+    RiskRowsArgs a;
+    a.X = X;
+    a.labels = labels;
+    a.weff = weff;
+    a.cached = cached;
+    a.B = B;
+    a.S = S;
+    a.F = F;
+    a.mode = mode;
+    a.lt = lt;
+    a.n_cached = n_cached;
+    a.cache_stride = cache_stride;
+    a.nsys = n_systems;
+    a.mat = mat;
+    a.R = R;
+    const long long tiles = ((long long)B * S + kTile - 1) / kTile;
+    if (grid > tiles) grid = (int)tiles;
+    const size_t lds = risk_rows_lds_bytes(F);
+    hipStream_t s = (hipStream_t)stream;
+    if (input_norm) {
+        if (int rc = set_lds(linear_risk_rows_kernel<true>, lds)) return rc;
+        hipLaunchKernelGGL(linear_risk_rows_kernel<true>, ltr_grid(grid), dim3(256), lds, s, a);
+    } else {
+        if (int rc = set_lds(linear_risk_rows_kernel<false>, lds)) return rc;
+        hipLaunchKernelGGL(linear_risk_rows_kernel<false>, ltr_grid(grid), dim3(256), lds, s, a);
+    }
+    return launch_status();
+}
+
+int ltr_linear_risk_combine(const float *R, const float *dmat, int dmat_stride, int B, int F, float *partials, int grid, void *stream) {
+    if (!R || !dmat || !partials) return LTR_ERR_NULL;
+    if (B < 1 || F < 1 || F > kLinMaxF || dmat_stride < 1) return LTR_ERR_SHAPE;
+    if (grid < 1 || grid > LTR_GRID_X_MAX) return LTR_ERR_PARAM;
+    hipLaunchKernelGGL(linear_risk_combine_kernel, ltr_grid(grid), dim3(256), 0, (hipStream_t)stream, R, dmat, dmat_stride, B, F + 1,
+                       partials);
+    return launch_status();
 }
 
 int ltr_linear_grid(int n_cus) {

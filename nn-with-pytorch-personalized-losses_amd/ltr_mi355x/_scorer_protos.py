@@ -32,6 +32,8 @@ PROTOTYPES = {
     "ltr_linear_fused_supported": (c_int, [c_int, c_int]),
     "ltr_linear_fused_step": (c_int, [c_int, P, P, c_int, c_int, c_int, P, c_int, c_float, c_float, c_float, c_int, c_int, c_int,
                                       c_float, c_float, c_float, c_int, c_float, P, P, P, c_int, P]),
+    "ltr_linear_risk_rows": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, c_int, P]),
+    "ltr_linear_risk_combine": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P]),
     "ltr_linear_grid": (c_int, [c_int]),
 }
 

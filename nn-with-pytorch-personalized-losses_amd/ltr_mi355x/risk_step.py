@@ -186,3 +186,47 @@ def scores_grad(h, spec, scores, yy, jac, coef_ptr, nsys, ds):
               "ltr_lambda_colsum_sys_bwd_coef")
     else:
         check(h.ltr_risk_scores_grad(_ptr(jac), coef_ptr, nsys, B, S, _ptr(ds), _stream()), "ltr_risk_scores_grad")
+
+
+def matrix_rows(spec, device, dp, B, nsys, world_batch):
+    """Where a step writes its [B, nsys] matrix rows -> (mat, send, bmax).  dp = (group, rank, world).  One process: a dense matrix
+    (send is None).  Data parallel (world > 1): the rows sit inside this rank's block of the gather -- padded to the largest shard `bmax`,
+    behind one float holding the row count."""
+    import torch.distributed as dist
+    group, _, world = dp
+    if world <= 1:
+        return torch.empty((B, nsys), dtype=torch.float32, device=device), None, B
+    if world_batch:
+        bmax = -(-int(world_batch) // world)
+    else:                                     # one size exchange (as QueryShardedTrainer.global_batch_of)
+        t = torch.tensor([B], dtype=torch.int64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+        bmax = int(t.item())
+    if B > bmax:
+        raise ValueError(f"{spec.name}: this rank holds {B} queries, more than ceil(global batch / world) = {bmax}: shard with "
+                         "ltr_mi355x.dp.shard_range")
+    send = torch.empty(1 + bmax * nsys, dtype=torch.float32, device=device)
+    send[:1].fill_(float(B))
+    return send[1:1 + B * nsys].view(B, nsys), send, bmax
+
+
+def run_tail(h, spec, dp, loss_slot, mat, send, bmax, B, nsys):
+    """[ONE all_gather of the padded row blocks ->] the tail on the whole matrix, its value into `loss_slot` (rank 0 alone under data
+    parallel: the all-reduced slot holds the global value once) -> (device address of d value / d mat of this rank's first row, the
+    tensor it points into)."""
+    import torch.distributed as dist
+    dev = mat.device
+    if send is None:
+        dmat = torch.empty((B, nsys), dtype=torch.float32, device=dev)
+        tail(h, spec, mat, B, nsys, loss_slot, dmat)
+        return dmat.data_ptr(), dmat
+    group, rank, world = dp
+    stride = send.numel()
+    recv = torch.empty((world, stride), dtype=torch.float32, device=dev)
+    dist.all_gather(list(recv.unbind(0)), send, group=group)
+    drecv = torch.empty_like(recv)
+    value = loss_slot if rank == 0 else torch.empty(1, dtype=torch.float32, device=dev)
+    tail_blocks(h, spec, recv, world, bmax, nsys, value, drecv)
+    if rank != 0:
+        loss_slot.fill_(0.0)
+    return drecv.data_ptr() + 4 * (rank * stride + 1), drecv

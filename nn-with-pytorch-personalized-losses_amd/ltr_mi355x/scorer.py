@@ -646,32 +646,14 @@ class FusedRanker:
     def _step_risk(self, h, x2, yy, B, S, dropout, seed, k1, k2, risk_in, world_batch, fold, pf, net, packed, partials):
         """Scorer forward (activations saved) -> matrix rows + Jacobian -> [all_gather] -> tail -> scores gradient -> scorer backward
         -> reduce (ltr_mi355x.risk_step)."""
-        import torch.distributed as dist
         from . import risk_step as RS
         R = self.risk
         yb, cache, n_c = risk_in
         nsys = 1 + n_c
         dev = self.device
         n = B * S
-        world, rank = self.risk_world, self.risk_rank
-        dp = world > 1
-        if dp:
-            # every rank's rows, padded to the largest shard, behind one float holding the row count
-            if world_batch:
-                bmax = -(-int(world_batch) // world)
-            else:                                     # one size exchange (as QueryShardedTrainer.global_batch_of)
-                t = torch.tensor([B], dtype=torch.int64, device=dev)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.risk_group)
-                bmax = int(t.item())
-            if B > bmax:
-                raise ValueError(f"{R.name}: this rank holds {B} queries, more than ceil(global batch / world) = {bmax}: shard with "
-                                 "ltr_mi355x.dp.shard_range")
-            stride = 1 + bmax * nsys
-            send = torch.empty(stride, dtype=torch.float32, device=dev)
-            send[:1].fill_(float(B))
-            mat = send[1:1 + B * nsys].view(B, nsys)
-        else:
-            mat = torch.empty((B, nsys), dtype=torch.float32, device=dev)
+        dp = (self.risk_group, self.risk_rank, self.risk_world)
+        mat, send, bmax = RS.matrix_rows(R, dev, dp, B, nsys, world_batch)
         scores = torch.empty(n, dtype=torch.float32, device=dev)
         jac = torch.empty(n, dtype=torch.float32, device=dev)
         if B > 0:
@@ -681,20 +663,7 @@ class FusedRanker:
             check(h.ltr_mlp_forward_save(net, _ptr(x2), n, _ptr(packed), int(dropout), seed, _ptr(k1), _ptr(k2),
                                          _ptr(scores), _ptr(self._acts), self.grid, _stream()), "ltr_mlp_forward_save")
             RS.matrix(h, R, scores, yy, yb, cache, n_c, mat, jac)
-        loss_slot = self.flat[self.info.n_params:self.info.n_params + 1]
-        if dp:
-            recv = torch.empty((world, stride), dtype=torch.float32, device=dev)
-            dist.all_gather(list(recv.unbind(0)), send, group=self.risk_group)
-            drecv = torch.empty_like(recv)
-            value = loss_slot if rank == 0 else torch.empty(1, dtype=torch.float32, device=dev)
-            RS.tail_blocks(h, R, recv, world, bmax, nsys, value, drecv)
-            if rank != 0:
-                loss_slot.fill_(0.0)                  # the all-reduced loss slot holds the global value once
-            coef = drecv.data_ptr() + 4 * (rank * stride + 1)
-        else:
-            dmat = torch.empty((B, nsys), dtype=torch.float32, device=dev)
-            RS.tail(h, R, mat, B, nsys, loss_slot, dmat)
-            coef = dmat.data_ptr()
+        coef, _dmat = RS.run_tail(h, R, dp, self.flat[self.info.n_params:self.info.n_params + 1], mat, send, bmax, B, nsys)
         if B == 0:
             self.flat_grad.zero_()
             return self._loss_out
