@@ -85,7 +85,11 @@ int ltr_lambda_fwd_bwd(const float *scores, const float *labels, int B, int S, i
 
 /* ---- lambdaMask(..., return_losses=True)                                losses/lambdaL.py:7-60
  * losses[b, ri, rj] for ALL pairs in predicted-rank order (ri, rj = 0-based ranks), optional keep mask
- * (the boolean mask of :62, 1 byte per pair) and rank[b, i] = predicted rank of document i. */
+ * (the boolean mask of :62, 1 byte per pair) and optional rank[b, i] = predicted rank of document i: ranks by
+ * counting, ties by index (the lower index first); padded documents rank after every real one, among themselves
+ * by index.  A pair with a padded document holds the same expression with that document's score -inf, gain 0 and
+ * clamped label 0 (d = clamp(s_i - s_j, +-1e8), NaN -> 0): max(w log_b(eps), log_b(eps)) when the first document
+ * is padded, 0 when only the second is, w log_b(1/2) when both are; keep is 0 there.  Every entry is written. */
 int ltr_lambda_pairs_fwd(const float *scores, const float *labels, int B, int S, int scheme, int k, float sigma,
                          float mu, float eps, float pad, int log_base, float *losses, uint8_t *keep,
                          int32_t *rank, void *stream);

@@ -39,6 +39,16 @@ inline SlateLaunch plan(int B, int S, int arrays_per_slate) {
     return L;
 }
 
+// Threads per slate of the one-slate-per-workgroup pair kernels: at least 256, but never more than one wave of column groups
+// per row -- row_reduce combines the CG replicas of a row inside ONE wave (CG <= 64), and 256 threads on S <= 2 documents
+// would make CG 128 / 256 (doubled rank counts at S = 2).  64 threads at S = 1, 128 at S = 2, unchanged from S = 3 on.
+inline int pair_group(int S) {
+    int g = pick_group(S) < 256 ? 256 : pick_group(S);
+    const int np2 = next_pow2(S);
+    while (g / (np2 < g ? np2 : g) > LTR_WAVE) g >>= 1;
+    return g;
+}
+
 template <class K>
 inline int allow_lds(K kernel, size_t lds) {
     if (lds <= 64 * 1024) return LTR_OK;
@@ -232,6 +242,16 @@ lambda_pairs_fwd_kernel(const float *__restrict__ scores, const float *__restric
     }
 }
 
+// One term of a column sum, compensated (Kahan): a column of S near-equal terms (rankNet weights on tied scores: every term
+// log_b(1/2)) summed naively in fp32 rounds the same way at every step and drifts by S ulp -- 1.5e-5 relative at S = 2048,
+// past the 1e-5 parity bar.  The three column-sum kernels share this step, so they stay bitwise equal to each other.
+__device__ __forceinline__ void colsum_add(float &acc, float &comp, float term) {
+    const float yk = term - comp;
+    const float tk = acc + yk;
+    comp = (tk - acc) - yk;
+    acc = tk;
+}
+
 // Column sums of the pair matrix, c[b, rj] = sum_ri losses[b, ri, rj] (what the risk losses take from
 // lambdaMask(return_losses=True): torch.sum(..., dim=1), riskLosses.py:72-83) WITHOUT materialising [B,S,S].
 template <int SCH>
@@ -260,7 +280,7 @@ lambda_colsum_fwd_kernel(const float *__restrict__ scores, const float *__restri
         const bool pj = L.gn[j] < 0.f;
         const float sj = pj ? -INFINITY : L.sc[j];
         const float Gj = fmaxf(L.gn[j], 0.f), ycj = fmaxf(L.yl[j], 0.f);
-        float acc = 0.f;
+        float acc = 0.f, comp = 0.f;
         for (int ri = 0; ri < S; ++ri) {          // rank order: the order torch.sum(dim=1) walks the column in
             const int i = dar[ri];
             const bool pi = L.gn[i] < 0.f;
@@ -273,7 +293,7 @@ lambda_colsum_fwd_kernel(const float *__restrict__ scores, const float *__restri
             float ell, dl;
             lambda_pair_term(P, lambda_weight<SCH>(P, L.delta, L.rk[i], L.rk[j], L.invd[i], L.invd[j], L.w1[i], Gi, Gj, yci, ycj),
                              u, um, ell, dl);
-            acc += ell;
+            colsum_add(acc, comp, ell);
         }
         colsum[off + rj] = acc;
     }
@@ -389,7 +409,7 @@ lambda_colsum_sys_fwd_kernel(const float *__restrict__ y_pred, const float *__re
         const bool pj = L.gn[j] < 0.f;
         const float sj = pj ? -INFINITY : L.sc[j];
         const float Gj = fmaxf(L.gn[j], 0.f), ycj = fmaxf(L.yl[j], 0.f);
-        float acc = 0.f;
+        float acc = 0.f, comp = 0.f;
         for (int ri = 0; ri < S; ++ri) {          // rank order: the order torch.sum(dim=1) walks the column in
             const int i = dar[ri];
             const bool pi = L.gn[i] < 0.f;
@@ -402,7 +422,7 @@ lambda_colsum_sys_fwd_kernel(const float *__restrict__ y_pred, const float *__re
             float ell, dl;
             lambda_pair_term(P, lambda_weight<SCH>(P, L.delta, L.rk[i], L.rk[j], L.invd[i], L.invd[j], L.w1[i], Gi, Gj, yci, ycj),
                              u, um, ell, dl);
-            acc += ell;
+            colsum_add(acc, comp, ell);
         }
         out[rj] = acc;
     }
@@ -469,7 +489,7 @@ lambda_risk_model_fwd_kernel(const float *__restrict__ y_pred, const float *__re
         const bool pj = L.gn[j] < 0.f;
         const float sj = pj ? -INFINITY : L.sc[j];
         const float Gj = fmaxf(L.gn[j], 0.f), ycj = fmaxf(L.yl[j], 0.f);
-        float acc = 0.f;
+        float acc = 0.f, comp = 0.f;
         for (int ri = 0; ri < S; ++ri) {          // rank order: the order torch.sum(dim=1) walks the column in
             const int i = dar[ri];
             const bool pi = L.gn[i] < 0.f;
@@ -482,7 +502,7 @@ lambda_risk_model_fwd_kernel(const float *__restrict__ y_pred, const float *__re
             float ell, dl;
             lambda_pair_term(P, lambda_weight<SCH>(P, L.delta, L.rk[i], L.rk[j], L.invd[i], L.invd[j], L.w1[i], Gi, Gj, yci, ycj),
                              u, um, ell, dl);
-            acc += ell;
+            colsum_add(acc, comp, ell);
         }
         x[rj] = acc;
     }
@@ -808,7 +828,7 @@ int ltr_lambda_pairs_fwd(const float *scores, const float *labels, int B, int S,
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
-    const int group = pick_group(S) < 256 ? 256 : pick_group(S);
+    const int group = pair_group(S);
     const size_t lds = (size_t)((kLambdaArrays + 1) * ((S + 3) & ~3) + group + 32) * sizeof(float);
 #define CALL(SCH)                                                                                                 \
     if (int rc = allow_lds(lambda_pairs_fwd_kernel<SCH>, lds)) return rc;                                         \
@@ -827,7 +847,7 @@ int ltr_lambda_pairs_bwd(const float *scores, const float *labels, int B, int S,
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
-    const int group = pick_group(S) < 256 ? 256 : pick_group(S);
+    const int group = pair_group(S);
     const size_t lds = (size_t)(kLambdaArrays * ((S + 3) & ~3) + group + 32) * sizeof(float);
 #define CALL(SCH)                                                                                                 \
     if (int rc = allow_lds(lambda_pairs_bwd_kernel<SCH>, lds)) return rc;                                         \
@@ -863,7 +883,7 @@ int ltr_lambda_colsum_bwd(const float *scores, const float *labels, int B, int S
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
-    const int group = pick_group(S) < 256 ? 256 : pick_group(S);
+    const int group = pair_group(S);
     const size_t lds = (size_t)(kLambdaArrays * ((S + 3) & ~3) + group + 32) * sizeof(float);
 #define CALL(SCH)                                                                                                 \
     if (int rc = allow_lds(lambda_pairs_bwd_kernel<SCH>, lds)) return rc;                                         \
@@ -899,7 +919,7 @@ int ltr_lambda_colsum_sys_bwd(const float *y_pred, const float *y_true, int B, i
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
-    const int group = pick_group(S) < 256 ? 256 : pick_group(S);
+    const int group = pair_group(S);
     const size_t lds = (size_t)((kLambdaArrays + 1) * ((S + 3) & ~3) + group + 32) * sizeof(float);
 #define CALL(SCH)                                                                                                 \
     if (int rc = allow_lds(lambda_colsum_sys_bwd_kernel<SCH>, lds)) return rc;                                    \
@@ -940,7 +960,7 @@ int ltr_lambda_colsum_sys_bwd_coef(const float *y_pred, const float *y_true, int
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
-    const int group = pick_group(S) < 256 ? 256 : pick_group(S);
+    const int group = pair_group(S);
     const size_t lds = (size_t)((kLambdaArrays + 1) * ((S + 3) & ~3) + group + 32) * sizeof(float);
 #define CALL(SCH)                                                                                                 \
     if (int rc = allow_lds(lambda_colsum_sys_bwd_kernel<SCH>, lds)) return rc;                                    \

@@ -182,12 +182,10 @@ def scheme_weights(scheme, G, D, mu, yc):
     raise KeyError(scheme)
 
 
-def lambda_pairs(y_pred, y_true, eps=1e-10, pad=-1, weighing_scheme=None, k=None, sigma=1.0, mu=10.0,
-                 reduction_log="binary"):
-    """Full pair-loss matrix and keep-mask, both [B,S,S] indexed by PREDICTED RANK (what
-    lambdaMask(return_losses=True) returns, lambdaL.py:59-60, plus the mask of :62)."""
-    if reduction_log not in ("binary", "natural"):
-        raise ValueError("Reduction logarithm base can be either natural or binary")
+def lambda_pair_parts(y_pred, y_true, eps=1e-10, pad=-1, weighing_scheme=None, k=None, mu=10.0):
+    """(w, d, keep), each [B,S,S] (w broadcastable) in PREDICTED-RANK order: the pair weight, the clamped score
+    difference (NaN -> 0) and the keep-mask of lambdaL.py:62 -- everything of a pair term but sigmoid / pow / log, so a
+    test can look at the unclamped `w log u` of every pair."""
     B, S = y_pred.shape
     dev = y_pred.device
     padm = y_true == pad
@@ -216,6 +214,16 @@ def lambda_pairs(y_pred, y_true, eps=1e-10, pad=-1, weighing_scheme=None, k=None
     w = scheme_weights(weighing_scheme, G, D, mu, ybc)
     d = (ss[:, :, None] - ss[:, None, :]).clamp(min=-1e8, max=1e8)
     d = torch.where(torch.isnan(d), torch.zeros_like(d), d)
+    return w, d, keep
+
+
+def lambda_pairs(y_pred, y_true, eps=1e-10, pad=-1, weighing_scheme=None, k=None, sigma=1.0, mu=10.0,
+                 reduction_log="binary"):
+    """Full pair-loss matrix and keep-mask, both [B,S,S] indexed by PREDICTED RANK (what
+    lambdaMask(return_losses=True) returns, lambdaL.py:59-60, plus the mask of :62)."""
+    if reduction_log not in ("binary", "natural"):
+        raise ValueError("Reduction logarithm base can be either natural or binary")
+    w, d, keep = lambda_pair_parts(y_pred, y_true, eps, pad, weighing_scheme, k, mu)
     P = (torch.sigmoid(sigma * d).clamp(min=eps) ** w).clamp(min=eps)
     losses = torch.log2(P) if reduction_log == "binary" else torch.log(P)
     return losses, keep

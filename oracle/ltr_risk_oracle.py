@@ -82,9 +82,9 @@ def _cos(a, b):
     return torch.nn.functional.cosine_similarity(a, b, dim=1)
 
 
-def pair_colsum(p, p_true, scheme):
+def pair_colsum(p, p_true, scheme, k=None, sigma=1.0, pad=-1, reduction_log="binary", mu=10.0):
     """torch.sum(lambdaMask(p, p_true, weighing_scheme=scheme, return_losses=True), dim=1): [B,S] by predicted rank."""
-    full, _ = O.lambda_pairs(p, p_true, weighing_scheme=scheme)
+    full, _ = O.lambda_pairs(p, p_true, pad=pad, weighing_scheme=scheme, k=k, sigma=sigma, mu=mu, reduction_log=reduction_log)
     return full.sum(dim=1)
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import lambda_tier_cases as LT
 import ltr_oracle as O
 from conftest import golden, golden_cases, relerr
 
@@ -94,6 +95,8 @@ def test_ordinal_golden(case, dev):
 
 # ----------------------------------------------------------------------------- oracle, fresh inputs
 SHAPES = [(1, 1), (3, 2), (5, 7), (9, 32), (6, 100), (2, 128), (3, 250), (2, 1000), (1, 2048)]
+# both sides of every launch-geometry edge of pick_group / plan (csrc/ltr_device.h, csrc/ltr_losses.hip), which approxNDCG and ListNet share
+SHAPES += [(5, 16), (5, 17), (3, 64), (3, 65), (2, 256), (2, 257), (2, 513), (2, 1024), (2, 1025), (1, 2047)]
 
 
 def _inputs(B, S, seed, padded):
@@ -131,20 +134,45 @@ def test_listnet_oracle(B, S, dev):
     assert relerr(l3.cpu().numpy(), O.listnet_closed_form(y.double(), s.double())[0].numpy()) < TOL
 
 
-@pytest.mark.parametrize("B,S", [(1, 1), (3, 2), (5, 7), (9, 32), (6, 100), (2, 128), (2, 512), (1, 1000)])
+LAMBDA_SHAPES = [(1, 1), (3, 2), (5, 7), (9, 32), (6, 100), (2, 128), (2, 512), (1, 1000)]
+LAMBDA_OPTS = ((None, "sum", "binary", 1.0), (5, "mean", "natural", 2.0))
+
+
+def _check_lambda(s, y, kw, dev, msg):
+    from losses.lambdaL import lambdaLoss
+    rl, rg, n = O.lambda_loss_closed_form(s.double(), y.double(), **kw)
+    loss, grad = run(lambda p: lambdaLoss(p, y.to(dev), **kw), s.to(dev))
+    if int(n) == 0 and kw["reduction"] == "mean":
+        assert np.isnan(loss)
+        return
+    assert relerr(loss, rl.numpy()) < TOL, msg
+    assert relerr(grad, rg.numpy()) < TOL, msg
+
+
+@pytest.mark.parametrize("B,S", LAMBDA_SHAPES + LT.EDGE_SHAPES)
 @pytest.mark.parametrize("scheme", list(O.SCHEMES))
 def test_lambda_oracle(B, S, scheme, dev):
-    from losses.lambdaL import lambdaLoss
-    s, y = _inputs(B, S, 300 + S, padded=(S % 2 == 0))
-    for k, red, lg, sigma in ((None, "sum", "binary", 1.0), (5, "mean", "natural", 2.0)):
+    """LT.EDGE_SHAPES: both sides of ltr_lambda_fwd_bwd's own dispatch edges (lambda_blocked_kernel takes 256 <= S <= 1024 except
+    under ndcgLoss1, lambda_kernel the rest) and of the 1024-thread / strided-row regimes.  Their scores come from the score-scale
+    ladder of lambda_tier_cases (no kept pair within 1e-4 of a clamp in the fp64 oracle), per option set."""
+    for k, red, lg, sigma in LAMBDA_OPTS:
         kw = dict(weighing_scheme=scheme, k=k, sigma=sigma, mu=10.0, reduction=red, reduction_log=lg)
-        rl, rg, n = O.lambda_loss_closed_form(s.double(), y.double(), **kw)
-        loss, grad = run(lambda p: lambdaLoss(p, y.to(dev), **kw), s.to(dev))
-        if int(n) == 0 and red == "mean":
-            assert np.isnan(loss)
-            continue
-        assert relerr(loss, rl.numpy()) < TOL, (k, red, lg)
-        assert relerr(grad, rg.numpy()) < TOL, (k, red, lg)
+        if (B, S) in LT.EDGE_SHAPES:
+            s, y = LT.edge_inputs("plain", B, S, scheme, k, sigma, lg)
+        else:
+            s, y = _inputs(B, S, 300 + S, padded=(S % 2 == 0))
+        _check_lambda(s, y, kw, dev, (k, red, lg))
+
+
+@pytest.mark.parametrize("B,S", LT.EDGE_SHAPES)
+@pytest.mark.parametrize("scheme", list(O.SCHEMES))
+def test_lambda_oracle_tied_scores(B, S, scheme, dev):
+    """Equal scores at the dispatch edges: the header's rule is "ranks by counting, ties by index", which is O.rank_desc; the
+    doc-space lambda_kernel and the rank-space lambda_blocked_kernel must both follow it."""
+    for k, red, lg, sigma in LAMBDA_OPTS:
+        kw = dict(weighing_scheme=scheme, k=k, sigma=sigma, mu=10.0, reduction=red, reduction_log=lg)
+        s, y = LT.edge_inputs("tied_scores", B, S, scheme, k, sigma, lg)
+        _check_lambda(s, y, kw, dev, (k, red, lg))
 
 
 def test_ordinal_oracle(dev):

@@ -72,7 +72,8 @@ def test_risk_functions_vs_oracle(Q, n, dev):
 
 
 @pytest.mark.parametrize("S", [8, 32, 128, 200])
-@pytest.mark.parametrize("scheme", ["ndcgLoss2PP_scheme", "lamdbaRank_scheme", "ndcgLoss1_scheme", None])
+@pytest.mark.parametrize("scheme", ["ndcgLoss2PP_scheme", "lamdbaRank_scheme", "ndcgLoss1_scheme", None, "ndcgLoss2_scheme", "rankNet_scheme",
+                                    "rankNetWeightedByGTDiff_scheme", "rankNetWeightedByGTDiffPowed_scheme"])
 def test_pair_colsum_vs_oracle(S, scheme, dev):
     """Column sums of the pair matrix without the [B,S,S] tensor == sum(dim=1) of the oracle's full matrix; also equal
     to summing this package's own lambdaMask(return_losses=True); and the backward."""
