@@ -207,6 +207,36 @@ enum { LTR_GAINS_LINEAR = 0, LTR_GAINS_EXPONENTIAL = 1 };
 int ltr_ndcg_at_k(const float *y_true, const float *y_score, int Q, int S, int k, int gains, int no_relevant,
                   int reverse_ties, double *ndcg, double *dcg, void *stream);
 
+/* =====================================================================================================
+ * Ragged batches: queries of unequal length, no padding (a LETOR file as distributed: utils/dataset.py:44-69 builds per-query
+ * lists, utils/metrics.py:77-80 loops over them).  scores / labels / dscores are [n_docs]; offsets [Q + 1] (int64, device,
+ * ascending, offsets[0] = 0): query q owns rows offsets[q] .. offsets[q + 1] - 1, 1 .. LTR_MAX_SLATE of them.  slate_loss,
+ * slate_count, ndcg and dcg are indexed by QUERY id, dscores by document row.
+ *   queries / n_queries : the query ids this launch handles (int32, device); queries == NULL: 0 .. n_queries - 1.
+ *   s_max               : an upper bound of the listed queries' lengths; launch geometry and LDS size come from it as the
+ *                         rectangular entry point derives them from S.
+ * The loss launches take ONE length tier at a time: every listed query has next_pow2(length) == next_pow2(s_max) (that power of
+ * two fixes threads per slate, row lanes / column groups and every barrier count, so slates of unequal length can share a
+ * workgroup).  A caller covers a batch with one launch per occupied tier (ltr_mi355x.ragged.RaggedSlates builds the lists).  The
+ * offsets live on the device and are not read by the host: a listed query outside the tier is not computed -- its slate_loss /
+ * ndcg slot becomes NaN, its count 0, its dscores rows stay untouched.  ltr_ndcg_at_k_ragged takes any lengths <= s_max.
+ * Queries that are not listed keep their slots and rows untouched.  With all listed lengths equal to S the results are the bits
+ * of the rectangular entry point at (n_queries, S).  Each loss is the reference's loss on every query as a batch of one; the
+ * caller combines slate_loss as for the rectangular twin (mean / sum / sum over total count).  k truncates on each query's own
+ * ranks.  n_queries < 0, s_max outside 1 .. LTR_MAX_SLATE: LTR_ERR_SHAPE. */
+int ltr_approxndcg_ragged_fwd_bwd(const float *scores, const float *labels, const int64_t *offsets, const int32_t *queries,
+                                  int n_queries, int s_max, float alpha, float eps, float pad, float grad_scale, float *slate_loss,
+                                  float *dscores, void *stream);
+int ltr_listnet_ragged_fwd_bwd(const float *y_true, const float *y_pred, const int64_t *offsets, const int32_t *queries,
+                               int n_queries, int s_max, int apply_sigmoid, float grad_scale, float *slate_loss, float *dscores,
+                               void *stream);
+int ltr_lambda_ragged_fwd_bwd(const float *scores, const float *labels, const int64_t *offsets, const int32_t *queries,
+                              int n_queries, int s_max, int scheme, int k, float sigma, float mu, float eps, float pad,
+                              int log_base, float grad_scale, float *slate_loss, float *slate_count, float *dscores,
+                              void *stream);
+int ltr_ndcg_at_k_ragged(const float *y_true, const float *y_score, const int64_t *offsets, const int32_t *queries, int n_queries,
+                         int s_max, int k, int gains, int no_relevant, int reverse_ties, double *ndcg, double *dcg, void *stream);
+
 /* ---- ordinalLoss(y_pred[B,S,n], y_true[B,S], n, padded_value_indicator)  losses/ordinal.py:27-53
  * n_docs = B*S documents, n ordinal probabilities each.  Targets 1[y >= k] are built with the default
  * indicator -1 (ordinal.py:39), then entries whose target == pad are masked (:41-45).

@@ -705,6 +705,190 @@ reduce_sum_kernel(const float *__restrict__ in, int64_t n, float scale, float *_
     }
 }
 
+// ------------------------------------------------------------------------------------------------ ragged batches
+// Query q owns document rows offsets[q] .. offsets[q + 1] - 1; a launch handles the queries of an index list (NULL: 0 .. n - 1) that
+// share ONE length tier: next_pow2(length) == next_pow2(s_max).  pick_group, make_group's row lanes / column groups and every loop
+// with a barrier inside the slate functions depend on the length only through that power of two, so slates of unequal length that
+// share a 256-thread workgroup (lengths <= 64) reach every barrier the same number of times, and a launch of equal lengths runs the
+// rectangular kernels' geometry exactly (same bits).  LDS is carved at the tier's s_max; each slate stages, zero-fills and pads up
+// to its OWN aligned length inside its slice.  A listed query whose length does not belong to the tier (the host layer never
+// lists one) gets a NaN loss and no gradient rows: nothing is read or written outside its slice.
+struct RaggedSlot {
+    long long q;     // query id (index into offsets / slate_loss)
+    size_t off;      // first document row
+    int S;           // documents; s_max for an idle slot
+    bool active;     // a listed query of this tier
+    bool misfit;     // a listed query whose length is outside the tier
+};
+
+// A slate group is a whole number of waves, so everything about its query is wave-uniform: taking the slot through
+// v_readfirstlane keeps the query id, the offset and above all the length S -- and with it the whole group geometry -- in scalar
+// registers, as the rectangular kernels have S in a kernel argument.
+__device__ __forceinline__ long long wave_uniform(long long v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return ((long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ RaggedSlot ragged_slot(const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries,
+                                                  long long slot, int n_queries, int s_max) {
+    slot = wave_uniform(slot);
+    RaggedSlot r;
+    r.q = 0;
+    r.off = 0;
+    r.S = s_max;
+    r.active = false;
+    r.misfit = false;
+    if (slot < n_queries) {
+        r.q = queries ? (long long)queries[slot] : slot;
+        const int64_t a = offsets[r.q], len = offsets[r.q + 1] - a;
+        if (len >= 1 && len <= s_max && next_pow2((int)len) == next_pow2(s_max)) {
+            r.off = (size_t)a;
+            r.S = (int)len;
+            r.active = true;
+        } else {
+            r.misfit = true;
+        }
+    }
+    return r;
+}
+
+__global__ void __launch_bounds__(1024)
+approxndcg_ragged_kernel(const float *__restrict__ scores, const float *__restrict__ labels, const int64_t *__restrict__ offsets,
+                         const int32_t *__restrict__ queries, int n_queries, int s_max, int group, float alpha, float eps,
+                         float pad, float gscale, float *__restrict__ slate_loss, float *__restrict__ dscores) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int s_cap = (s_max + 3) & ~3;
+    const int gid = threadIdx.x / group;
+    const RaggedSlot rq = ragged_slot(offsets, queries, ltr_block_id() * (blockDim.x / group) + gid, n_queries, s_max);
+    const int S = rq.S;
+    const bool active = rq.active;
+    float *base = smem + (size_t)gid * (kApproxArrays * s_cap + group + 32);
+    float *sc = base, *yl = sc + s_cap, *gn = yl + s_cap, *gg = gn + s_cap, *uu = gg + s_cap, *mk = uu + s_cap;
+    ApproxScratch xs;
+    xs.um = mk + s_cap;
+    const SlateGroup g = make_group(S, group, xs.um + s_cap);
+    const size_t off = rq.off;
+    approx_ndcg_init(g);
+    for (int j = g.t; j < S; j += group) {
+        const float y = active ? labels[off + j] : pad;
+        sc[j] = active ? scores[off + j] : 0.f;
+        stage_label(y, pad, yl[j], gn[j]);
+    }
+    __syncthreads();
+    float *dst = dscores ? dscores + off : nullptr;
+    const float loss = approx_ndcg_slate(g, sc, yl, gn, gg, uu, mk, alpha, eps, gscale, dscores != nullptr,
+                                         [&](int i, float v) { if (active) dst[i] = v; }, NoStamp(), xs);
+    if (g.t == 0 && (active || rq.misfit)) slate_loss[rq.q] = active ? loss : NAN;
+}
+
+__global__ void __launch_bounds__(1024)
+listnet_ragged_kernel(const float *__restrict__ y_true, const float *__restrict__ y_pred, const int64_t *__restrict__ offsets,
+                      const int32_t *__restrict__ queries, int n_queries, int s_max, int group, int apply_sigmoid, float gscale,
+                      float *__restrict__ slate_loss, float *__restrict__ dscores) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int s_cap = (s_max + 3) & ~3;
+    const int gid = threadIdx.x / group;
+    const RaggedSlot rq = ragged_slot(offsets, queries, ltr_block_id() * (blockDim.x / group) + gid, n_queries, s_max);
+    const int S = rq.S;
+    const bool active = rq.active;
+    float *base = smem + (size_t)gid * (2 * s_cap + group + 32);
+    float *yt = base, *yp = yt + s_cap;
+    const SlateGroup g = make_group(S, group, yp + s_cap);
+    const size_t off = rq.off;
+    for (int j = g.t; j < S; j += group) {
+        yt[j] = active ? y_true[off + j] : 0.f;
+        yp[j] = active ? y_pred[off + j] : 0.f;
+    }
+    __syncthreads();
+    float *dst = dscores ? dscores + off : nullptr;
+    const float loss = listnet_slate(g, yt, yp, apply_sigmoid != 0, gscale, dscores != nullptr,
+                                     [&](int i, float v) { if (active) dst[i] = v; });
+    if (g.t == 0 && (active || rq.misfit)) slate_loss[rq.q] = active ? loss : NAN;
+}
+
+template <int SCH>
+__global__ void __launch_bounds__(1024)
+lambda_ragged_kernel(const float *__restrict__ scores, const float *__restrict__ labels, const int64_t *__restrict__ offsets,
+                     const int32_t *__restrict__ queries, int n_queries, int s_max, int group, LambdaParams P, float pad,
+                     float gscale, float *__restrict__ slate_loss, float *__restrict__ slate_count,
+                     float *__restrict__ dscores) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int s_cap = (s_max + 3) & ~3;
+    const int gid = threadIdx.x / group;
+    const RaggedSlot rq = ragged_slot(offsets, queries, ltr_block_id() * (blockDim.x / group) + gid, n_queries, s_max);
+    const int S = rq.S;
+    const bool active = rq.active;
+    float *base = smem + (size_t)gid * (kLambdaArrays * s_cap + group + 32);
+    const LambdaLds L = lambda_carve(base, s_cap);
+    const SlateGroup g = make_group(S, group, base + kLambdaArrays * s_cap);
+    const size_t off = rq.off;
+    for (int j = g.t; j < S; j += group) {
+        const float y = active ? labels[off + j] : pad;
+        L.sc[j] = active ? scores[off + j] : 0.f;
+        stage_label(y, pad, L.yl[j], L.gn[j]);
+    }
+    __syncthreads();
+    float *dst = dscores ? dscores + off : nullptr;
+    float count;
+    const float loss = lambda_slate<SCH>(g, L, P, gscale, dscores != nullptr, &count,
+                                         [&](int i, float v) { if (active) dst[i] = v; });
+    if (g.t == 0 && (active || rq.misfit)) {
+        slate_loss[rq.q] = active ? loss : NAN;
+        slate_count[rq.q] = active ? count : 0.f;
+    }
+}
+
+// The rank-space sweep (lambda_blocked_kernel) on a ragged tier: one slate per workgroup of 64 ceil(s_max / 64) threads; the waves
+// past a shorter slate's last rank block idle through lambda_slate_blocked's barriers.
+template <int SCH>
+__global__ void __launch_bounds__(1024)
+lambda_blocked_ragged_kernel(const float *__restrict__ scores, const float *__restrict__ labels,
+                             const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries, int n_queries, int s_max,
+                             LambdaParams P, float pad, float gscale, float *__restrict__ slate_loss,
+                             float *__restrict__ slate_count, float *__restrict__ dscores) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int s_cap = (s_max + 3) & ~3, s64_cap = (s_max + 63) & ~63;
+    const RaggedSlot rq = ragged_slot(offsets, queries, ltr_block_id(), n_queries, s_max);
+    if (!rq.active) {                            // (whole block: one slate per workgroup)
+        if (rq.misfit && threadIdx.x == 0) {
+            slate_loss[rq.q] = NAN;
+            slate_count[rq.q] = 0.f;
+        }
+        return;
+    }
+    const int S = rq.S;
+    const LambdaLds L = lambda_carve(smem, s_cap);
+    float *rb = smem + kLambdaArrays * s_cap;
+    LambdaRankLds R;
+    R.rs = rb;
+    R.ry = rb + s64_cap;
+    R.rg = rb + 2 * s64_cap;
+    R.colacc = rb + 3 * s64_cap;
+    R.doc_of = reinterpret_cast<int *>(rb + 4 * s64_cap);
+    const SlateGroup g = make_group(S, blockDim.x, rb + 5 * s64_cap);
+    const size_t off = rq.off;
+    for (int j = g.t; j < S; j += blockDim.x) {
+        L.sc[j] = scores[off + j];
+        stage_label(labels[off + j], pad, L.yl[j], L.gn[j]);
+    }
+    __syncthreads();
+    float *dst = dscores ? dscores + off : nullptr;
+    float count;
+    const float loss = lambda_slate_blocked<SCH>(g, L, R, P, gscale, dscores != nullptr, &count,
+                                                 [&](int i, float v) { dst[i] = v; });
+    if (g.t == 0) {
+        slate_loss[rq.q] = loss;
+        slate_count[rq.q] = count;
+    }
+}
+
+inline int check_ragged(const void *a, const void *b, const void *c, const void *offsets, int n_queries, int s_max) {
+    if (!a || !b || !c || !offsets) return LTR_ERR_NULL;
+    if (n_queries < 0 || s_max < 1 || s_max > LTR_MAX_SLATE) return LTR_ERR_SHAPE;
+    return LTR_OK;
+}
+
 inline int make_lambda_params(int scheme, int k, float sigma, float mu, float eps, int log_base, LambdaParams *P) {
     if (scheme < 0 || scheme > 7) return LTR_ERR_PARAM;
     if (log_base != LTR_LOG_BINARY && log_base != LTR_LOG_NATURAL) return LTR_ERR_PARAM;
@@ -966,6 +1150,70 @@ int ltr_lambda_colsum_sys_bwd_coef(const float *y_pred, const float *y_true, int
     if (int rc = allow_lds(lambda_colsum_sys_bwd_kernel<SCH>, lds)) return rc;                                    \
     hipLaunchKernelGGL(lambda_colsum_sys_bwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, y_pred, y_true, B, S, \
                        group, P, pad, jac, coef, coef_stride, dy_pred)
+    LTR_DISPATCH_SCHEME(scheme, CALL)
+#undef CALL
+    return launch_status();
+}
+
+int ltr_approxndcg_ragged_fwd_bwd(const float *scores, const float *labels, const int64_t *offsets, const int32_t *queries,
+                                  int n_queries, int s_max, float alpha, float eps, float pad, float grad_scale, float *slate_loss,
+                                  float *dscores, void *stream) {
+    if (int rc = check_ragged(scores, labels, slate_loss, offsets, n_queries, s_max)) return rc;
+    if (n_queries == 0) return LTR_OK;
+    const SlateLaunch L = plan(n_queries, s_max, kApproxArrays);
+    if (int rc = allow_lds(approxndcg_ragged_kernel, L.lds)) return rc;
+    hipLaunchKernelGGL(approxndcg_ragged_kernel, ltr_grid(L.grid), dim3(L.block), L.lds, (hipStream_t)stream, scores, labels,
+                       offsets, queries, n_queries, s_max, L.group, alpha, eps, pad, grad_scale, slate_loss, dscores);
+    return launch_status();
+}
+
+int ltr_listnet_ragged_fwd_bwd(const float *y_true, const float *y_pred, const int64_t *offsets, const int32_t *queries,
+                               int n_queries, int s_max, int apply_sigmoid, float grad_scale, float *slate_loss, float *dscores,
+                               void *stream) {
+    if (int rc = check_ragged(y_true, y_pred, slate_loss, offsets, n_queries, s_max)) return rc;
+    if (n_queries == 0) return LTR_OK;
+    // ltr_listnet_fwd_bwd's geometry: one thread per document
+    const int group = next_pow2(s_max) < 64 ? 64 : (next_pow2(s_max) > 1024 ? 1024 : next_pow2(s_max));
+    const int block = group < 256 ? 256 : group, gpb = block / group;
+    const size_t lds = (size_t)gpb * (2 * ((s_max + 3) & ~3) + group + 32) * sizeof(float);
+    hipLaunchKernelGGL(listnet_ragged_kernel, ltr_grid((n_queries + gpb - 1) / gpb), dim3(block), lds, (hipStream_t)stream, y_true,
+                       y_pred, offsets, queries, n_queries, s_max, group, apply_sigmoid, grad_scale, slate_loss, dscores);
+    return launch_status();
+}
+
+int ltr_lambda_ragged_fwd_bwd(const float *scores, const float *labels, const int64_t *offsets, const int32_t *queries,
+                              int n_queries, int s_max, int scheme, int k, float sigma, float mu, float eps, float pad,
+                              int log_base, float grad_scale, float *slate_loss, float *slate_count, float *dscores,
+                              void *stream) {
+    if (int rc = check_ragged(scores, labels, slate_loss, offsets, n_queries, s_max)) return rc;
+    if (!slate_count) return LTR_ERR_NULL;
+    LambdaParams P;
+    if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
+    if (n_queries == 0) return LTR_OK;
+    if (s_max >= 256 && s_max <= 1024 && scheme != LTR_SCHEME_NDCG_LOSS1) {       // ltr_lambda_fwd_bwd's dispatch, on the tier's s_max
+        const int s_al = (s_max + 3) & ~3, s64 = (s_max + 63) & ~63;
+        const size_t lds = (size_t)(kLambdaArrays * s_al + 5 * s64 + s64 + 32) * sizeof(float);
+#define CALLB(SCH)                                                                                                \
+    if (int rc = allow_lds(lambda_blocked_ragged_kernel<SCH>, lds)) return rc;                                    \
+    hipLaunchKernelGGL(lambda_blocked_ragged_kernel<SCH>, ltr_grid(n_queries), dim3(s64), lds, (hipStream_t)stream, scores, \
+                       labels, offsets, queries, n_queries, s_max, P, pad, grad_scale, slate_loss, slate_count, dscores)
+        switch (scheme) {
+            case 0: { CALLB(0); break; }
+            case 2: { CALLB(2); break; }
+            case 3: { CALLB(3); break; }
+            case 4: { CALLB(4); break; }
+            case 5: { CALLB(5); break; }
+            case 6: { CALLB(6); break; }
+            default: { CALLB(7); break; }
+        }
+#undef CALLB
+        return launch_status();
+    }
+    const SlateLaunch L = plan(n_queries, s_max, kLambdaArrays);
+#define CALL(SCH)                                                                                                 \
+    if (int rc = allow_lds(lambda_ragged_kernel<SCH>, L.lds)) return rc;                                          \
+    hipLaunchKernelGGL(lambda_ragged_kernel<SCH>, ltr_grid(L.grid), dim3(L.block), L.lds, (hipStream_t)stream, scores, labels, \
+                       offsets, queries, n_queries, s_max, L.group, P, pad, grad_scale, slate_loss, slate_count, dscores)
     LTR_DISPATCH_SCHEME(scheme, CALL)
 #undef CALL
     return launch_status();

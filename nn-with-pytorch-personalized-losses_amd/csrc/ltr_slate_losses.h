@@ -1235,7 +1235,9 @@ __device__ __forceinline__ float lambda_slate_blocked(const SlateGroup &g, const
     float ls = 0.f, cn = 0.f, gr = 0.f;
     for (int t = 0; 2 * t <= nb; ++t) {
         const int u = v + t < nb ? v + t : v + t - nb;         // column block of this round
-        const bool active = (2 * t < nb) || (v < nb / 2);      // t == nb/2 (even nb): each block pair only once
+        // t == nb/2 (even nb): each block pair only once.  v >= nb: a wave past the slate's last rank block (a ragged launch sizes the
+        // workgroup for the longest slate of its tier) only keeps the barriers company
+        const bool active = v < nb && ((2 * t < nb) || (v < nb / 2));
         float colreg = 0.f;                                    // lane c holds the column-side sum of column 64 u + c
         if (active) {
             for (int c0 = 0; c0 < 64; ++c0) {

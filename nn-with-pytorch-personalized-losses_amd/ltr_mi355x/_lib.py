@@ -53,6 +53,12 @@ _PROTOTYPES = {
     "ltr_risk_tail_fwd_bwd": (c_int, [P, c_int, c_int, c_float, c_int, c_int, c_int, c_float, c_int, P, P, P]),
     "ltr_risk_matrix_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "ltr_ndcg_at_k": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    # ragged batches (offsets / queries / n_queries / s_max in place of B, S)
+    "ltr_approxndcg_ragged_fwd_bwd": (c_int, [P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, P, P, P]),
+    "ltr_listnet_ragged_fwd_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P, P, P]),
+    "ltr_lambda_ragged_fwd_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
+                                          c_float, P, P, P, P]),
+    "ltr_ndcg_at_k_ragged": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "ltr_svmlight_scan": (c_int, [c_char_p, P, P, P, c_int]),
     "ltr_svmlight_load": (c_int, [c_char_p, c_int64, c_int, c_int, P, P, P, c_int]),
     "ltr_gather_rows_f32": (c_int, [P, c_int64, P, c_int64, c_int64, P, P]),

@@ -1,0 +1,440 @@
+"""Queries of unequal length without padding: the host side of the ltr_*_ragged_* entry points (include/ltr_mi355x.h).
+
+A ragged batch is `scores [n_docs]`, `labels [n_docs]` (for a training step: `X [n_docs, F]`) plus a `RaggedSlates`, which holds
+the int64 offsets (query q owns rows offsets[q] .. offsets[q + 1] - 1) and, per LENGTH TIER, the sorted list of the queries in it.
+The loss kernels pick their launch geometry from the slate length (csrc/ltr_device.h pick_group / make_group), so a ragged batch
+runs as one launch per occupied tier over that tier's query list; inside a tier every length has the same next power of two and
+with it the same threads per slate, row lanes, column groups and barrier counts.
+
+Each loss is the reference's loss on every query as a batch of one, combined by the reference's own reduction: approxNDCG the mean
+over the queries (approxNDCG.py:53), ListNet the sum (listnet.py:16), lambdaLoss the sum of the kept-pair terms, or that sum over
+the total kept-pair count for reduction="mean" (lambdaL.py:88-89).
+
+    X, y, qid = load_svmlight(path)
+    slates = RaggedSlates.from_qid(qid, device="cuda")
+    Xd, yd = torch.as_tensor(X, device="cuda"), torch.as_tensor(y, device="cuda", dtype=torch.float32)
+    for q0 in range(0, slates.n_queries, 2000):
+        b = slates.batch(q0, min(q0 + 2000, slates.n_queries))
+        d0, d1 = slates.doc_range(q0, q0 + b.n_queries)
+        loss = ranker.step_ragged(Xd[d0:d1], yd[d0:d1], b)
+"""
+import functools
+
+import numpy as np
+import torch
+
+from ._lib import check, lib
+from .functional import MAX_SLATE, SCHEME_IDS, _f32, _lambda_args, _ptr, _reduce, _stream, require_device   # noqa: F401
+
+# Upper ends of the length tiers.  Powers of two (the geometry rule above), with 256 on its own: lambdaLoss sends 256 .. 1024
+# down the rank-space kernel (every scheme but ndcgLoss1), 129 .. 255 down the document-order one.
+TIER_HI = (1, 2, 4, 8, 16, 32, 64, 128, 255, 256, 512, 1024, 2048)
+
+
+def tier_of(sizes):
+    """Index into TIER_HI of every length in `sizes` (1 .. MAX_SLATE)."""
+    return np.searchsorted(np.asarray(TIER_HI), np.asarray(sizes), side="left")
+
+
+class RaggedSlates:
+    """The query structure of a ragged collection or batch: host sizes / offsets, device int64 offsets and one device int32 array
+    `order` holding the query ids sorted by (tier, id), with the host array `tier_start` marking each tier's slice.
+
+    bounds: [Q + 1] ascending integers with bounds[0] = 0 (ltr_mi355x.data.query_bounds).  Every query has 1 .. 2048 documents;
+    anything else is a ValueError here, before any launch.  The device arrays are made on first use (`device=` or `.to(device)`)."""
+
+    def __init__(self, bounds, device=None):
+        b = np.asarray(bounds)
+        if b.ndim != 1 or b.size < 1:
+            raise ValueError(f"bounds must be a 1-D array of Q + 1 offsets, got shape {b.shape}")
+        if b.dtype.kind not in "iu":
+            raise ValueError(f"bounds must be integers, got {b.dtype}")
+        b = b.astype(np.int64)
+        if b[0] != 0:
+            raise ValueError(f"bounds[0] must be 0, got {int(b[0])}")
+        sizes = np.diff(b)
+        if sizes.size and (sizes < 1).any():
+            q = int(np.flatnonzero(sizes < 1)[0])
+            raise ValueError(f"query {q} has {int(sizes[q])} documents: offsets must ascend strictly (no empty query)")
+        if sizes.size and (sizes > MAX_SLATE).any():
+            q = int(np.flatnonzero(sizes > MAX_SLATE)[0])
+            raise ValueError(f"query {q} has {int(sizes[q])} documents, outside the supported range 1..{MAX_SLATE}")
+        self.offsets_host = b
+        self.sizes = sizes
+        tiers = tier_of(sizes)
+        self.order_host = np.argsort(tiers, kind="stable").astype(np.int32)            # by tier, then by query id
+        self.tier_start = np.searchsorted(tiers[self.order_host], np.arange(len(TIER_HI) + 1), side="left").astype(np.int64)
+        self.device = None
+        self.offsets = self.order = None
+        self._tiers = None
+        if device is not None:
+            self.to(device)
+
+    @classmethod
+    def from_qid(cls, qid, device=None):
+        """From the per-document query ids of a LETOR file (a new query starts where qid changes, utils/dataset.py:54-60)."""
+        from .data import query_bounds
+        return cls(query_bounds(qid), device=device)
+
+    @classmethod
+    def _made(cls, offsets_host, order_host, tier_start, device, offsets, order):
+        self = cls.__new__(cls)
+        self.offsets_host, self.sizes = offsets_host, np.diff(offsets_host)
+        self.order_host, self.tier_start = order_host, tier_start
+        self.device, self.offsets, self.order = device, offsets, order
+        self._tiers = None
+        return self
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            from ._lib import LtrDeviceError
+            raise LtrDeviceError("RaggedSlates' device arrays feed HIP kernels: they live on a ROCm device")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.device != device:
+            self.offsets = torch.as_tensor(self.offsets_host, device=device)
+            self.order = torch.as_tensor(self.order_host, device=device)
+            self.device = device
+        return self
+
+    @property
+    def n_queries(self):
+        return int(self.sizes.size)
+
+    @property
+    def n_docs(self):
+        return int(self.offsets_host[-1])
+
+    @property
+    def max_len(self):
+        return int(self.sizes.max()) if self.sizes.size else 0
+
+    def doc_range(self, q0, q1):
+        """(first row, one past the last row) of queries q0 .. q1 - 1."""
+        return int(self.offsets_host[q0]), int(self.offsets_host[q1])
+
+    def tiers(self):
+        """[(s_max, start, count)] per OCCUPIED tier: order[start : start + count] are its queries (ascending ids), s_max the longest."""
+        if self._tiers is None:
+            out = []
+            for t in range(len(TIER_HI)):
+                a, b = int(self.tier_start[t]), int(self.tier_start[t + 1])
+                if b > a:
+                    out.append((int(self.sizes[self.order_host[a:b]].max()), a, b - a))
+            self._tiers = out
+        return self._tiers
+
+    def batch(self, q0, q1):
+        """The sub-batch of the consecutive queries q0 .. q1 - 1: offsets rebased to its first document, tier lists sliced (each
+        tier's list is sorted by query id, so a range of ids is one contiguous slice of it) and rebased to q0.  Host arithmetic
+        and device slicing only: nothing waits for the device."""
+        q0, q1 = int(q0), int(q1)
+        if not 0 <= q0 <= q1 <= self.n_queries:
+            raise ValueError(f"batch({q0}, {q1}) outside 0..{self.n_queries}")
+        off_h = self.offsets_host[q0:q1 + 1] - self.offsets_host[q0]
+        cuts, start = [], [0]
+        for t in range(len(TIER_HI)):
+            a, b = int(self.tier_start[t]), int(self.tier_start[t + 1])
+            seg = self.order_host[a:b]
+            lo, hi = a + int(np.searchsorted(seg, q0, side="left")), a + int(np.searchsorted(seg, q1, side="left"))
+            cuts.append((lo, hi))
+            start.append(start[-1] + hi - lo)
+        order_h = (np.concatenate([self.order_host[lo:hi] for lo, hi in cuts]) - q0).astype(np.int32) if cuts else self.order_host[:0]
+        offsets = order = None
+        if self.device is not None:
+            offsets = self.offsets[q0:q1 + 1] - int(self.offsets_host[q0])
+            parts = [self.order[lo:hi] for lo, hi in cuts if hi > lo]
+            order = (torch.cat(parts) - q0) if parts else self.order[:0]
+        return RaggedSlates._made(off_h, order_h, np.asarray(start, dtype=np.int64), self.device, offsets, order)
+
+    def permuted(self, perm):
+        """Queries in the order `perm` (a permutation of 0 .. Q - 1, host array or tensor): returns (new_slates, doc_index) where
+        doc_index [n_docs] int64 (on the slates' device when they have one) lists the old document rows in their new order --
+        `gather_rows(X, doc_index)`, `gather_rows(y[:, None], doc_index)` is the ragged counterpart of EpochShuffler."""
+        p = perm.detach().cpu().numpy() if torch.is_tensor(perm) else np.asarray(perm)
+        p = p.astype(np.int64)
+        if p.shape != (self.n_queries,) or not np.array_equal(np.sort(p), np.arange(self.n_queries)):
+            raise ValueError(f"perm must be a permutation of 0..{self.n_queries - 1}")
+        sizes = self.sizes[p]
+        bounds = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+        # row r of new query j is old row offsets[p[j]] + (r - bounds[j])
+        doc = np.repeat(self.offsets_host[:-1][p] - bounds[:-1], sizes) + np.arange(int(bounds[-1]), dtype=np.int64)
+        new = RaggedSlates(bounds, device=self.device)
+        idx = torch.as_tensor(doc, device=self.device) if self.device is not None else torch.as_tensor(doc)
+        return new, idx
+
+
+# ------------------------------------------------------------------------------------------------------- launches
+def _flat(t, name, n_docs):
+    if t.dim() == 2 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 1 or int(t.shape[0]) != n_docs:
+        raise ValueError(f"{name} must have shape [n_docs] = [{n_docs}], got {tuple(t.shape)}")
+    return t
+
+
+def _slates_on(slates, dev):
+    if not isinstance(slates, RaggedSlates):
+        raise TypeError(f"slates must be a RaggedSlates, got {type(slates).__name__}")
+    return slates.to(dev)
+
+
+def launch_loss(h, kind, slates, scores, labels, slate_loss, count, ds, scale, args):
+    """One launch per occupied tier of `slates`.  kind 0 approxNDCG (args = alpha, eps, pad), 1 ListNet (args = apply_sigmoid;
+    `labels` are y_true), 2 lambdaLoss (args = _lambda_args).  Pointers are raw device addresses (None = NULL)."""
+    off = slates.offsets.data_ptr()
+    base = slates.order.data_ptr()
+    for s_max, a, n in slates.tiers():
+        q = base + 4 * a
+        if kind == 0:
+            alpha, eps, pad = args
+            check(h.ltr_approxndcg_ragged_fwd_bwd(scores, labels, off, q, n, s_max, alpha, eps, pad, scale, slate_loss, ds, _stream()),
+                  "ltr_approxndcg_ragged_fwd_bwd")
+        elif kind == 1:
+            check(h.ltr_listnet_ragged_fwd_bwd(labels, scores, off, q, n, s_max, int(args), scale, slate_loss, ds, _stream()),
+                  "ltr_listnet_ragged_fwd_bwd")
+        else:
+            sid, kk, sigma, mu, eps, pad, lb = args
+            check(h.ltr_lambda_ragged_fwd_bwd(scores, labels, off, q, n, s_max, sid, kk, sigma, mu, eps, pad, lb, scale, slate_loss,
+                                              count, ds, _stream()), "ltr_lambda_ragged_fwd_bwd")
+
+
+@functools.lru_cache(maxsize=None)
+def _ragged_loss():
+    """The autograd node of the three ragged losses.  Built on first use rather than at module level: tests/test_autograd_state_cpu.py
+    pairs every module-level Function of the package with an entry of the table in tests/test_autograd_state_gpu.py; this node's
+    state test (inputs changed between forward and backward) is tests/test_ragged_gpu.py::test_backward_uses_forward_time_state.  Its
+    backward reads nothing but the gradient the forward launches saved."""
+    class _RaggedLoss(torch.autograd.Function):
+        """One autograd node for the three losses: forward and d loss / d scores in the forward launches, gradient to the scores only."""
+
+        @staticmethod
+        def forward(ctx, scores, labels, slates, kind, args, reduction):
+            require_device(scores, labels)
+            slates = _slates_on(slates, scores.device)
+            n, Q = slates.n_docs, slates.n_queries
+            s_in, y_in = _flat(scores, "scores", n), _flat(labels, "labels", n)
+            out_dtype = torch.result_type(scores, labels)
+            ctx.in_dtype, ctx.in_shape = scores.dtype, scores.shape
+            dev = scores.device
+            lambda_mean = kind == 2 and reduction == "mean"
+            if Q == 0 or (kind == 2 and args[1] < 0):
+                # the reference's reductions of nothing: mean -> nan, sum -> 0 (k = 0 keeps no pair, lambdaL.py:29-30); zero gradient
+                ctx.save_for_backward(torch.zeros(n, dtype=torch.float32, device=dev))
+                v = float("nan") if (lambda_mean or (kind == 0 and Q == 0)) else 0.0
+                return torch.full((), v, dtype=out_dtype, device=dev)
+            with torch.cuda.device(dev):
+                s, y = _f32(s_in), _f32(y_in)
+                slate = torch.empty(Q, dtype=torch.float32, device=dev)
+                count = torch.empty(Q, dtype=torch.float32, device=dev) if kind == 2 else None
+                ds = torch.empty(n, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+                scale = 1.0 / Q if kind == 0 else 1.0
+                launch_loss(lib(), kind, slates, _ptr(s), _ptr(y), _ptr(slate), _ptr(count), _ptr(ds), scale, args)
+                loss = _reduce(slate, scale)
+                if lambda_mean:
+                    nk = _reduce(count, 1.0)
+                    loss = loss / nk
+                    if ds is not None:
+                        ds = ds / torch.where(nk > 0, nk, torch.ones_like(nk))      # no kept pair: nan loss, zero gradients
+            ctx.save_for_backward(ds)
+            return loss.to(out_dtype)
+
+        @staticmethod
+        def backward(ctx, go):
+            (ds,) = ctx.saved_tensors
+            return (ds * go.to(torch.float32)).to(ctx.in_dtype).reshape(ctx.in_shape), None, None, None, None, None
+    return _RaggedLoss
+
+
+def approx_ndcg(scores, labels, slates, eps=1e-10, padded_value_indicator=-1, alpha=1.):
+    """approxNDCGLoss (losses/approxNDCG.py:7-53) on a ragged batch: the mean over the queries of each query's own loss."""
+    return _ragged_loss().apply(scores, labels, slates, 0, (float(alpha), float(eps), float(padded_value_indicator)), None)
+
+
+def listnet(y_true, y_pred, slates, apply_sigmoid=False):
+    """listnetLoss (losses/listnet.py:5-16) on a ragged batch: both softmaxes run over exactly the query's own documents; the sum."""
+    return _ragged_loss().apply(y_pred, y_true, slates, 1, bool(apply_sigmoid), None)
+
+
+def lambda_loss(scores, labels, slates, eps=1e-10, padded_value_indicator=-1, weighing_scheme=None, k=None, sigma=1., mu=10.,
+                reduction="sum", reduction_log="binary"):
+    """lambdaLoss (losses/lambdaL.py:67-93) on a ragged batch; `k` truncates on each query's own predicted ranks."""
+    args = _lambda_args(eps, padded_value_indicator, weighing_scheme, k, sigma, mu, reduction_log)
+    if reduction not in ("sum", "mean"):
+        raise ValueError("Reduction method can be either sum or mean")             # lambdaL.py:91
+    return _ragged_loss().apply(scores, labels, slates, 2, args, reduction)
+
+
+def ndcg_at_k(y_true, y_score, slates, k=5, no_relevant=True, gains="linear", reverse_ties=False, want="ndcg"):
+    """Per-query NDCG@k (or DCG@k) of a ragged batch, [Q] fp64 device tensor (utils/metrics.py:48-74 per query; k is clamped to
+    the query's own length, :54-55; k=None: every document).  Ranked in fp32 like ltr_mi355x.metrics.ndcg_at_k."""
+    from .metrics import GAINS, to_device_f32
+    if gains not in GAINS:
+        raise ValueError("Invalid gains option.")                                  # metrics.py:62
+    s = to_device_f32(y_score)
+    y = to_device_f32(y_true, like=s)
+    slates = _slates_on(slates, s.device)
+    n, Q = slates.n_docs, slates.n_queries
+    s, y = _flat(s, "y_score", n), _flat(y, "y_true", n)
+    out = torch.empty(Q, dtype=torch.float64, device=s.device)
+    kk = int(k) if k is not None else MAX_SLATE
+    with torch.cuda.device(s.device):
+        for s_max, a, cnt in slates.tiers():
+            check(lib().ltr_ndcg_at_k_ragged(_ptr(y), _ptr(s), _ptr(slates.offsets), slates.order.data_ptr() + 4 * a, cnt, s_max, kk,
+                                             GAINS[gains], int(bool(no_relevant)), int(bool(reverse_ties)),
+                                             _ptr(out) if want == "ndcg" else None, _ptr(out) if want == "dcg" else None,
+                                             _stream()), "ltr_ndcg_at_k_ragged")
+    return out
+
+
+def ndcg_of_lists(true_lists, pred_lists, **kw):
+    """utils.metrics.mNdcg's ragged route: a list of per-query label lists and the matching score lists -> [Q] fp64."""
+    if len(true_lists) != len(pred_lists):
+        raise ValueError(f"{len(true_lists)} label lists but {len(pred_lists)} score lists")
+    ys = [np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.float32).reshape(-1) for t in true_lists]
+    ss = [np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, dtype=np.float32).reshape(-1) for t in pred_lists]
+    for q, (a, b) in enumerate(zip(ys, ss)):
+        if a.size != b.size:
+            raise ValueError(f"query {q}: {a.size} labels but {b.size} scores")
+    slates = RaggedSlates(np.concatenate(([0], np.cumsum([a.size for a in ys]))).astype(np.int64))
+    return ndcg_at_k(np.concatenate(ys) if ys else np.zeros(0, np.float32), np.concatenate(ss) if ss else np.zeros(0, np.float32),
+                     slates, **kw)
+
+
+# ------------------------------------------------------------------------------------------------------- training step
+def step_ragged(ranker, X, y, slates, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False):
+    """FusedRanker.step_ragged: the three-launch chain (scorer forward with saved activations -> loss -> scorer backward; for the
+    folded make_model ranker scores -> loss -> gradient partials) with the ragged loss launches in the middle.  Same flat
+    [grads | loss | normaliser] buffer, same deferred-normalisation protocol as `step` (normaliser: the query count for approxNDCG,
+    the kept-pair count for lambdaLoss "mean")."""
+    from .scorer import LOSS_APPROXNDCG, LOSS_LAMBDA
+    self = ranker
+    if self.risk is not None:
+        raise NotImplementedError(f"{self.loss}: the risk-sensitive losses compare queries through one [queries x systems] matrix and "
+                                  "train on equal-length slates only: use the rectangular FusedRanker.step")
+    linear = not hasattr(self, "packed")
+    if linear:
+        self._check_trainable(train, keep1, keep2)
+    info = self.info
+    require_device(X, y)
+    slates = _slates_on(slates, X.device)
+    n, Q = slates.n_docs, slates.n_queries
+    if X.dim() != 2 or X.shape[1] != info.F or int(X.shape[0]) != n:
+        raise ValueError(f"expected X [n_docs = {n}, {info.F}], got {tuple(X.shape)}")
+    y1 = _flat(y, "y", n)
+    n_par = info.n_params
+    lambda_mean = self.loss_kind == LOSS_LAMBDA and self.reduction == "mean"
+    if lambda_mean and not defer_norm and world_batch not in (None, Q):
+        raise ValueError('lambdaLoss reduction="mean" divides by the GLOBAL kept-pair count, which no rank knows before '
+                         "the all-reduce: under data parallel call step_ragged(defer_norm=True)")
+    if Q == 0:
+        self.flat_ext.zero_()
+        if self.loss_kind == LOSS_APPROXNDCG and not world_batch and not defer_norm:
+            self.flat[n_par] = float("nan")
+        self._bind_grads()
+        return self._loss_out
+    if self.loss_kind == LOSS_LAMBDA and self.lambda_args[1] < 0:      # k = 0 keeps no pair
+        self.flat_ext.zero_()
+        if lambda_mean and not defer_norm:
+            self.flat[n_par] = float("nan")
+        self._bind_grads()
+        return self._loss_out
+    gb = int(world_batch) if world_batch else Q
+    scale = 1.0 / gb if (self.loss_kind == LOSS_APPROXNDCG and not defer_norm) else 1.0
+    if defer_norm and self.loss_kind == LOSS_APPROXNDCG:
+        self._norm.fill_(float(Q))
+    h = lib()
+    if self.loss_kind == LOSS_APPROXNDCG:
+        largs = (self.alpha, self.eps, self.pad)
+    elif self.loss_kind == LOSS_LAMBDA:
+        largs = self.lambda_args
+    else:
+        largs = self.apply_sigmoid
+    with torch.cuda.device(self.device):
+        yy = y1.detach().to(torch.float32).contiguous()
+        if self._slate is None or self._slate.numel() < Q:
+            self._slate = torch.empty(Q, dtype=torch.float32, device=self.device)
+        count = torch.empty(Q, dtype=torch.float32, device=self.device) if self.loss_kind == LOSS_LAMBDA else None
+
+        def loss_launches(scores, ds):
+            launch_loss(h, self.loss_kind, slates, _ptr(scores), _ptr(yy), _ptr(self._slate), _ptr(count), _ptr(ds), scale, largs)
+
+        if linear:
+            _linear_chain(self, h, X, n, loss_launches)
+        else:
+            _mlp_chain(self, h, X, n, keep1, keep2, seed, train, loss_launches)
+        check(h.ltr_reduce_sum_f32(_ptr(self._slate), Q, scale, self.flat.data_ptr() + 4 * n_par, _stream()), "ltr_reduce_sum_f32")
+        if lambda_mean:
+            torch.sum(count, dim=0, keepdim=True, out=self._norm)
+            if not defer_norm:
+                self._divide_by_norm()
+    self._bind_grads()
+    return self._loss_out
+
+
+def _mlp_chain(self, h, X, n, keep1, keep2, seed, train, loss_launches):
+    """FusedRanker._step_three_launches on [n_docs, F] rows."""
+    from . import scorer as S
+    info = self.info
+    train = self.module.training if train is None else train
+    dropout = S.drop_code(bool(train and self.module._ltr_dropout), getattr(getattr(self.module, "dropout", None), "p", 0.5))
+    if seed is None:
+        seed = S.next_seed(self._calls) ^ ((self.seed_salt * 0xA24BAED4963EE407) & S._MASK64)
+    seed = int(seed) & S._MASK64
+    self._calls += 1
+    dev = self.device
+    x2 = S._docs(X, info)
+    k1, k2 = S._mask(keep1, n, info.H1, info.cH1), S._mask(keep2, n, info.H2, info.cH2)
+    fold = self.fold32 if (k1 is None and k2 is None) else None
+    net, packed, partials, pf = self.net, self.packed, self.partials, None
+    if fold is None:
+        S.pack_params(info.handle, self.params, out=self.packed)
+    else:
+        pf = S._params_f32(self.params)
+        copies = fold.H1 // 32
+        fw = S.triple_fold(pf, copies, [self.fold_w[0][:fold.H1], self.fold_w[1][:fold.H1], self.fold_w[2][:, :fold.H1]])
+        packed = self.fold_packed[:fold.packed_floats]
+        S.pack_params(fold.handle, fw + [pf[5]], out=packed)
+        net, partials = fold.net, self.fold_partials
+    scores = torch.empty(n, dtype=torch.float32, device=dev)
+    ds = torch.empty(n, dtype=torch.float32, device=dev)
+    n_acts = int(h.ltr_mlp_acts_floats(net, n))
+    if self._acts is None or self._acts.numel() < n_acts:
+        self._acts = torch.empty(n_acts, dtype=torch.float32, device=dev)
+    check(h.ltr_mlp_forward_save(net, _ptr(x2), n, _ptr(packed), int(dropout), seed, _ptr(k1), _ptr(k2), _ptr(scores),
+                                 _ptr(self._acts), self.grid, _stream()), "ltr_mlp_forward_save")
+    loss_launches(scores, ds)
+    if self.kernel_events is not None:
+        self.kernel_events[0].record()
+    check(h.ltr_mlp_backward_saved(net, _ptr(x2), n, _ptr(packed), int(dropout), _ptr(self._acts), _ptr(ds), _ptr(partials),
+                                   self.grid, _stream()), "ltr_mlp_backward_saved")
+    if self.kernel_events is not None:
+        self.kernel_events[1].record()
+    self._reduce(fold, pf, partials, self.grid)
+
+
+def _linear_chain(self, h, X, n, loss_launches):
+    """LinearFusedRanker's fold -> _three_launches -> unfold on [n_docs, F] rows."""
+    info = self.info
+    F, L, ln = info.F, len(info.sizes), int(info.input_norm)
+    self._calls += 1
+    x2 = self._docs(X)
+    ps, ptrs = self._param_ptrs()
+    check(h.ltr_linear_fold(L, F, self._sizes, ln, ptrs, _ptr(self.ws), _ptr(self.weff), _stream()), "ltr_linear_fold")
+    if self.kernel_events is not None:
+        self.kernel_events[0].record()
+    if self._bufs is None or self._bufs[0].numel() < n:
+        self._bufs = [torch.empty(n, dtype=torch.float32, device=self.device),
+                      torch.empty(n, dtype=torch.float32, device=self.device),
+                      torch.empty(2 * n, dtype=torch.float32, device=self.device)]
+    scores, ds, stats = self._bufs
+    check(h.ltr_linear_scores(_ptr(x2), n, F, _ptr(self.weff), ln, _ptr(scores), _ptr(stats), _stream()), "ltr_linear_scores")
+    loss_launches(scores, ds)
+    check(h.ltr_linear_grad_partials(_ptr(x2), n, F, _ptr(ds), _ptr(stats), ln, _ptr(self.partials), self.grid, _stream()),
+          "ltr_linear_grad_partials")
+    if self.kernel_events is not None:
+        self.kernel_events[1].record()
+    check(h.ltr_linear_unfold_grads(L, F, self._sizes, ln, ptrs, _ptr(self.partials), self.grid, _ptr(self.ws), _ptr(self.flat_grad),
+                                    _stream()), "ltr_linear_unfold_grads")
+    del ps

@@ -555,6 +555,14 @@ class FusedRanker:
         self._bind_grads()
         return self._loss_out
 
+    def step_ragged(self, X, y, slates, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False):
+        """`step` for queries of unequal length, no padding: X [n_docs, F], y [n_docs], slates a ltr_mi355x.ragged.RaggedSlates
+        (query q owns rows offsets[q] .. offsets[q + 1] - 1).  The three-launch chain with one loss launch per occupied length tier;
+        buffers, return value, `world_batch` (here: the global QUERY count) and defer_norm / finish_norm as in `step`.  Explicit
+        masks are [n_docs, H].  approxNDCG, ListNet and lambdaLoss; the risk-sensitive losses raise NotImplementedError."""
+        from .ragged import step_ragged
+        return step_ragged(self, X, y, slates, world_batch, keep1, keep2, seed, train, defer_norm)
+
     def _reduce(self, fold, pf, partials, grid):
         """Per-workgroup partials -> the flat gradient of the module's own tensors (through the unfold for a folded TripleLayerNet)."""
         if fold is None:

@@ -20,7 +20,17 @@ def getGeoRiskDefault(mat, alpha):
     return _m.geo_risk_all_systems(mat, alpha).double().cpu().numpy()
 
 
+def _ragged(lists):
+    """A list of per-query lists of unequal length (what utils/dataset.py:44-69 builds from a LETOR file as distributed)."""
+    if not isinstance(lists, (list, tuple)) or not lists or not all(hasattr(q, "__len__") for q in lists):
+        return False
+    return len({len(q) for q in lists}) > 1
+
+
 def mNdcg_device(true_relevance, pred_relevance, k=5, no_relevant=True, gains='linear', use_numpy=False):
+    if _ragged(true_relevance):
+        from ltr_mi355x import ragged
+        return ragged.ndcg_of_lists(true_relevance, pred_relevance, k=k, no_relevant=no_relevant, gains=gains, reverse_ties=use_numpy)
     return _m.ndcg_at_k(true_relevance, pred_relevance, k=k, no_relevant=no_relevant, gains=gains, reverse_ties=use_numpy)
 
 
