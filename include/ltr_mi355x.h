@@ -237,6 +237,47 @@ int ltr_lambda_ragged_fwd_bwd(const float *scores, const float *labels, const in
 int ltr_ndcg_at_k_ragged(const float *y_true, const float *y_score, const int64_t *offsets, const int32_t *queries, int n_queries,
                          int s_max, int k, int gains, int no_relevant, int reverse_ties, double *ndcg, double *dcg, void *stream);
 
+/* ---- The six risk-sensitive losses on a ragged batch               losses/riskLosses/riskLosses.py:8-49, :63-117, :128-169, :183-236,
+ * :247-276, :294-330 behind main_batch_execution.py:140-165.  Entry mat[q][sys] of the effectiveness matrix is computed from query
+ * q's documents alone (softmaxes over its own slate, then a sum over the slate or over its predicted ranks), so row q is the row the
+ * reference computes for q inside any batch of queries of q's length, before the flip; the rows of all queries form one dense
+ * [Q][n_systems] matrix for the unchanged tails (ltr_risk_tail_fwd_bwd, ltr_trisk_tail_fwd_bwd and their *_blocks_* forms).
+ * offsets / queries / n_queries / s_max as above; n_docs = offsets[Q], the documents of the whole batch (host value: rows past it are
+ * never touched).  With all lengths equal to S every entry below gives the bits of its rectangular twin at (n_queries, S).
+ *
+ * ltr_risk_matrix_ragged_fwd: ltr_risk_matrix_rows_fwd (cached == NULL) / ltr_risk_matrix_cached_fwd (cached != NULL: n_rest cached
+ * entries per row at cached[q * cache_stride], ideal = ones = 0) with ref / x0 [n_docs], rest [n_docs][n_rest] (modes 0, 2;
+ * riskLosses.py:10-46, :249-268) or ref / x0 / rest ragged column sums, system k at rest[(k - 1) * n_docs] (mode 1; :71-106, :205-226,
+ * :312-322).  ONE launch for any lengths 1 .. s_max (256 threads per query whatever its length: no tier).  mat [Q][ld] is indexed by
+ * query id, jac [n_docs] by document row.  A listed query outside 1 .. s_max gets a NaN model entry, nothing else of it is touched. */
+int ltr_risk_matrix_ragged_fwd(const float *ref, const float *x0, const float *rest, const int64_t *offsets, const int32_t *queries,
+                               int n_queries, int s_max, int64_t n_docs, int n_rest, int mode, int lt, int ideal, int ones,
+                               const float *cached, int cache_stride, float *mat, float *jac, void *stream);
+/* dscores[d] = jac[d] * dmat[q(d) * dmat_stride] over the listed queries' rows (ltr_risk_scores_grad; the backward of
+ * riskLosses.py:8-49 / :128-169 / :247-276 through the scores).  One launch, one workgroup per query. */
+int ltr_risk_scores_grad_ragged(const float *jac, const float *dmat, int dmat_stride, const int64_t *offsets, const int32_t *queries,
+                                int n_queries, int64_t n_docs, float *dscores, void *stream);
+/* The Lambda forms' pair work, ONE length tier per launch like the ragged loss launches (a listed query outside the tier is not
+ * computed: its rows stay untouched, ltr_lambda_risk_model_ragged_fwd poisons its model entry with NaN).
+ * ltr_lambda_colsum_sys_ragged_fwd: ltr_lambda_colsum_sys_fwd (riskLosses.py:63-83, :183-203, :294-310), y_base [n_docs][n_base],
+ *   colsum [n_base + 2][n_docs]; one workgroup per (system, query).
+ * ltr_lambda_risk_model_ragged_fwd: ltr_lambda_risk_model_fwd (:84-106, :205-226, :312-322 for the model alone) with the cache split
+ *   into cache [Q][cache_stride] (n_cached matrix entries per query) and ideal_colsum [n_docs] (the ideal ranking's column sums, by
+ *   document row); mat [Q][1 + n_cached], jac [n_docs].  s_max >= 2.
+ * ltr_lambda_colsum_sys_ragged_bwd_coef: ltr_lambda_colsum_sys_bwd_coef (the backward of :72-83 / :192-203 / :302-310 for system 0),
+ *   d L / d colsum[0][d] = jac[d] * coef[q(d) * coef_stride] formed inside the launch. */
+int ltr_lambda_colsum_sys_ragged_fwd(const float *y_pred, const float *y_true, const float *y_base, const int64_t *offsets,
+                                     const int32_t *queries, int n_queries, int s_max, int64_t n_docs, int n_base, int scheme, int k,
+                                     float sigma, float mu, float eps, float pad, int log_base, float *colsum, void *stream);
+int ltr_lambda_risk_model_ragged_fwd(const float *y_pred, const float *y_true, const float *cache, int cache_stride,
+                                     const float *ideal_colsum, int n_cached, const int64_t *offsets, const int32_t *queries,
+                                     int n_queries, int s_max, int64_t n_docs, int scheme, int k, float sigma, float mu, float eps,
+                                     float pad, int log_base, int lt, float *mat, float *jac, void *stream);
+int ltr_lambda_colsum_sys_ragged_bwd_coef(const float *y_pred, const float *y_true, const int64_t *offsets, const int32_t *queries,
+                                          int n_queries, int s_max, int64_t n_docs, int scheme, int k, float sigma, float mu, float eps,
+                                          float pad, int log_base, const float *jac, const float *coef, int coef_stride, float *dy_pred,
+                                          void *stream);
+
 /* ---- ordinalLoss(y_pred[B,S,n], y_true[B,S], n, padded_value_indicator)  losses/ordinal.py:27-53
  * n_docs = B*S documents, n ordinal probabilities each.  Targets 1[y >= k] are built with the default
  * indicator -1 (ordinal.py:39), then entries whose target == pad are masked (:41-45).

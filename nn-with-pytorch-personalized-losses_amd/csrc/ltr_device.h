@@ -22,6 +22,13 @@ inline dim3 ltr_grid(long long blocks) {
     if (blocks <= LTR_GRID_X_MAX) return dim3((unsigned)(blocks > 0 ? blocks : 1));
     return dim3((unsigned)LTR_GRID_X_MAX, (unsigned)((blocks + LTR_GRID_X_MAX - 1) / LTR_GRID_X_MAX));
 }
+// A wave-uniform 64-bit value through v_readfirstlane (two 32-bit halves): the ragged kernels take a query's id, offset and length this
+// way, so the length S -- and the group geometry and loop bounds derived from it -- stay in scalar registers, as with a kernel argument.
+__device__ __forceinline__ long long ltr_wave_uniform(long long v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return ((long long)hi << 32) | lo;
+}
 #define LTR_LN2 0.69314718055994530942f
 
 namespace ltr {

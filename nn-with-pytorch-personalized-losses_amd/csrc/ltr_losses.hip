@@ -372,21 +372,16 @@ __device__ __forceinline__ void slate_softmax(const SlateGroup &g, float *v, int
     __syncthreads();
 }
 
+// One (system, slate): off = the slate's first document row, S its length, out = where its S column sums go.  Shared by the rectangular
+// kernel and the ragged one (same group size -> same bits).
 template <int SCH>
-__global__ void __launch_bounds__(1024)
-lambda_colsum_sys_fwd_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, const float *__restrict__ y_base, int B,
-                             int S, int nb, int group, LambdaParams P, float pad, float *__restrict__ colsum) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+__device__ __forceinline__ void colsum_sys_slate(const float *__restrict__ y_pred, const float *__restrict__ y_true,
+                                                 const float *__restrict__ y_base, const int sys, const size_t off, const int S, int nb,
+                                                 int group, const LambdaParams &P, float pad, float *__restrict__ out, float *base) {
     const int s_al = (S + 3) & ~3;
-    const long long blk = ltr_block_id();
-    if (blk >= (long long)(nb + 2) * B) return;  // (whole block: the y-padding of a two-dimensional grid)
-    const int sys = (int)(blk / B);
-    const long long slate = blk - (long long)sys * B;
-    float *base = smem;
     const LambdaLds L = lambda_carve(base, s_al);
     int *dar = reinterpret_cast<int *>(base + kLambdaArrays * s_al);   // document at rank r
     const SlateGroup g = make_group(S, group, base + (kLambdaArrays + 1) * s_al);
-    const size_t off = (size_t)slate * S;
     for (int j = g.t; j < S; j += group) {
         L.yl[j] = y_true[off + j];
         L.sc[j] = sys == 0 ? y_pred[off + j] : (sys <= nb ? y_base[(off + j) * nb + (sys - 1)] : 0.f);
@@ -403,7 +398,6 @@ lambda_colsum_sys_fwd_kernel(const float *__restrict__ y_pred, const float *__re
     lambda_prepare(g, L, P);
     for (int j = g.t; j < S; j += group) dar[L.rk[j]] = j;
     __syncthreads();
-    float *out = colsum + ((size_t)sys * B + slate) * S;
     for (int rj = g.t; rj < S; rj += group) {
         const int j = dar[rj];
         const bool pj = L.gn[j] < 0.f;
@@ -426,6 +420,19 @@ lambda_colsum_sys_fwd_kernel(const float *__restrict__ y_pred, const float *__re
         }
         out[rj] = acc;
     }
+}
+
+template <int SCH>
+__global__ void __launch_bounds__(1024)
+lambda_colsum_sys_fwd_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, const float *__restrict__ y_base, int B,
+                             int S, int nb, int group, LambdaParams P, float pad, float *__restrict__ colsum) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const long long blk = ltr_block_id();
+    if (blk >= (long long)(nb + 2) * B) return;  // (whole block: the y-padding of a two-dimensional grid)
+    const int sys = (int)(blk / B);
+    const long long slate = blk - (long long)sys * B;
+    colsum_sys_slate<SCH>(y_pred, y_true, y_base, sys, (size_t)slate * S, S, nb, group, P, pad,
+                          colsum + ((size_t)sys * B + slate) * S, smem);
 }
 
 // ---- The Lambda-type risk step with the constant systems cached (ltr_mi355x.scorer.FusedRanker.baseline_columns): the baselines' and the
@@ -452,26 +459,20 @@ __device__ __forceinline__ double eff_block_sum(double v, double *red, int nw) {
     return s;
 }
 
+// One slate: crow = its n_cached cached matrix entries, t = the ideal ranking's S column sums, mrow = its matrix row, off = its first
+// document row.  Shared by the rectangular kernel and the ragged one.
 template <int SCH>
-__global__ void __launch_bounds__(1024)
-lambda_risk_model_fwd_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, const float *__restrict__ cache,
-                             int cache_stride, int n_cached, int B, int S, int group, LambdaParams P, float pad, int lt,
-                             float *__restrict__ mat, float *__restrict__ jac) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ double red[kEffThreads / LTR_WAVE];
+__device__ __forceinline__ void risk_model_slate(const float *__restrict__ y_pred, const float *__restrict__ y_true,
+                                                 const float *__restrict__ crow, const float *__restrict__ t, int n_cached,
+                                                 const size_t off, const int S, int group,
+                                                 const LambdaParams &P, float pad, int lt, float *__restrict__ mrow,
+                                                 float *__restrict__ jac, float *base, double *red) {
     const int s_al = (S + 3) & ~3;
-    const long long slate = ltr_block_id();
-    if (slate >= B) return;                      // (whole block: the y-padding of a two-dimensional grid)
-    float *base = smem;
     const LambdaLds L = lambda_carve(base, s_al);
     int *dar = reinterpret_cast<int *>(base + kLambdaArrays * s_al);   // document at rank r
     float *x = base + (kLambdaArrays + 1) * s_al;                       // the model's column sums, by predicted rank
     const SlateGroup g = make_group(S, group, x + s_al);
-    const size_t off = (size_t)slate * S;
-    const float *crow = cache + (size_t)slate * cache_stride;           // [n_cached matrix entries | ideal column sums [S]]
-    const float *t = crow + n_cached;
-    const int nsys = 1 + n_cached;
-    for (int k = threadIdx.x; k < n_cached; k += group) mat[(size_t)slate * nsys + 1 + k] = crow[k];
+    for (int k = threadIdx.x; k < n_cached; k += group) mrow[1 + k] = crow[k];
     for (int j = g.t; j < S; j += group) {
         L.yl[j] = y_true[off + j];
         L.sc[j] = y_pred[off + j];
@@ -536,7 +537,7 @@ lambda_risk_model_fwd_kernel(const float *__restrict__ y_pred, const float *__re
     if (lt == 1) m = c;
     else if (lt == 2) m = a / den;
     else m = (sx - st) * (sx - st);
-    if (tid == 0) mat[(size_t)slate * nsys] = (float)m;
+    if (tid == 0) mrow[0] = (float)m;
     const double nv_c = nrm_v > 1e-8 ? nrm_v : 1e-8;
     const double inv_vv = nrm_v > 0.0 ? 1.0 / (nv_c * nrm_v) : 0.0;
     for (int j = tid; j < S; j += group) {
@@ -549,22 +550,32 @@ lambda_risk_model_fwd_kernel(const float *__restrict__ y_pred, const float *__re
     }
 }
 
-// d L / d y_pred from d L / d colsum[system 0]: the pair backward on the soft-maxed vectors, then the softmax's Jacobian
-// (d p_i / d s_k = p_i (delta_ik - p_k)):  ds_k = p_k (dp_k - sum_i p_i dp_i)
 template <int SCH>
 __global__ void __launch_bounds__(1024)
-lambda_colsum_sys_bwd_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, int B, int S, int group, LambdaParams P,
-                             float pad, const float *__restrict__ gup, const float *__restrict__ coef, int coef_stride,
-                             float *__restrict__ dy_pred) {
+lambda_risk_model_fwd_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, const float *__restrict__ cache,
+                             int cache_stride, int n_cached, int B, int S, int group, LambdaParams P, float pad, int lt,
+                             float *__restrict__ mat, float *__restrict__ jac) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int s_al = (S + 3) & ~3;
+    __shared__ double red[kEffThreads / LTR_WAVE];
     const long long slate = ltr_block_id();
-    if (slate >= B) return;
-    float *base = smem;
+    if (slate >= B) return;                      // (whole block: the y-padding of a two-dimensional grid)
+    const float *crow = cache + (size_t)slate * cache_stride;           // [n_cached matrix entries | ideal column sums [S]]
+    risk_model_slate<SCH>(y_pred, y_true, crow, crow + n_cached, n_cached, (size_t)slate * S, S, group, P, pad, lt,
+                          mat + (size_t)slate * (1 + n_cached), jac, smem, red);
+}
+
+// d L / d y_pred from d L / d colsum[system 0]: the pair backward on the soft-maxed vectors, then the softmax's Jacobian
+// (d p_i / d s_k = p_i (delta_ik - p_k)):  ds_k = p_k (dp_k - sum_i p_i dp_i)
+// One slate (off = its first document row, cq = its coefficient).  Shared by the rectangular kernel and the ragged one.
+template <int SCH>
+__device__ __forceinline__ void colsum_sys_bwd_slate(const float *__restrict__ y_pred, const float *__restrict__ y_true, const size_t off,
+                                                     const int S, int group, const LambdaParams &P, float pad,
+                                                     const float *__restrict__ gup, const float cq, float *__restrict__ dy_pred,
+                                                     float *base) {
+    const int s_al = (S + 3) & ~3;
     const LambdaLds L = lambda_carve(base, s_al);
     float *dp = base + kLambdaArrays * s_al;
     const SlateGroup g = make_group(S, group, dp + s_al);
-    const size_t off = (size_t)slate * S;
     for (int j = g.t; j < S; j += group) {
         L.yl[j] = y_true[off + j];
         L.sc[j] = y_pred[off + j];
@@ -576,8 +587,6 @@ lambda_colsum_sys_bwd_kernel(const float *__restrict__ y_pred, const float *__re
     __syncthreads();
     lambda_prepare(g, L, P);
     const float *G = gup + off;
-    // coef != NULL: d L / d colsum[0] = gup (the Jacobian of the model's matrix entry) x coef[slate] (d L / d mat[slate][0])
-    const float cq = coef ? coef[slate * coef_stride] : 1.f;
     for (int i0 = 0; i0 < S; i0 += g.sp) {
         const int i = i0 + g.ri;
         const bool row = i < S;
@@ -611,6 +620,19 @@ lambda_colsum_sys_bwd_kernel(const float *__restrict__ y_pred, const float *__re
     for (int j = g.t; j < S; j += group) dot += L.sc[j] * dp[j];
     dot = group_sum(g, dot);
     for (int j = g.t; j < S; j += group) dy_pred[off + j] = L.sc[j] * (dp[j] - dot);
+}
+
+template <int SCH>
+__global__ void __launch_bounds__(1024)
+lambda_colsum_sys_bwd_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, int B, int S, int group, LambdaParams P,
+                             float pad, const float *__restrict__ gup, const float *__restrict__ coef, int coef_stride,
+                             float *__restrict__ dy_pred) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const long long slate = ltr_block_id();
+    if (slate >= B) return;
+    // coef != NULL: d L / d colsum[0] = gup (the Jacobian of the model's matrix entry) x coef[slate] (d L / d mat[slate][0])
+    const float cq = coef ? coef[slate * coef_stride] : 1.f;
+    colsum_sys_bwd_slate<SCH>(y_pred, y_true, (size_t)slate * S, S, group, P, pad, gup, cq, dy_pred, smem);
 }
 
 // --------------------------------------------------------------------------------------- ordinal
@@ -724,11 +746,7 @@ struct RaggedSlot {
 // A slate group is a whole number of waves, so everything about its query is wave-uniform: taking the slot through
 // v_readfirstlane keeps the query id, the offset and above all the length S -- and with it the whole group geometry -- in scalar
 // registers, as the rectangular kernels have S in a kernel argument.
-__device__ __forceinline__ long long wave_uniform(long long v) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-    return ((long long)hi << 32) | lo;
-}
+__device__ __forceinline__ long long wave_uniform(long long v) { return ltr_wave_uniform(v); }
 
 __device__ __forceinline__ RaggedSlot ragged_slot(const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries,
                                                   long long slot, int n_queries, int s_max) {
@@ -881,6 +899,58 @@ lambda_blocked_ragged_kernel(const float *__restrict__ scores, const float *__re
         slate_loss[rq.q] = loss;
         slate_count[rq.q] = count;
     }
+}
+
+// ---- The Lambda-type risk losses on a ragged tier: the three kernels above with the slate taken from the
+// tier's query list.  ONE slate owns its workgroup, so an idle or misfit slot leaves as a whole block before the first barrier and
+// every barrier inside the slate functions is reached by all threads of the block (section 4.9's rule; no mixed-barrier site here).
+// The group size comes from the tier's s_max by the rectangular launcher's formula -- constant inside a tier, which depends on the
+// length through next_pow2 only -- so with all lengths equal these are the rectangular launches' bits.  n_docs = the documents of
+// the whole batch: system k's column sums start at colsum[k * n_docs].
+template <int SCH>
+__global__ void __launch_bounds__(1024)
+lambda_colsum_sys_ragged_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, const float *__restrict__ y_base,
+                                const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries, int n_queries, int s_max,
+                                long long n_docs, int nb, int group, LambdaParams P, float pad, float *__restrict__ colsum) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const long long blk = wave_uniform(ltr_block_id());
+    if (blk >= (long long)(nb + 2) * n_queries) return;      // (whole block: the y-padding of a two-dimensional grid)
+    const int sys = (int)(blk / n_queries);
+    const RaggedSlot rq = ragged_slot(offsets, queries, blk - (long long)sys * n_queries, n_queries, s_max);
+    if (!rq.active || rq.off + rq.S > (size_t)n_docs) return;      // (whole block) a query outside the tier: its rows stay untouched
+    colsum_sys_slate<SCH>(y_pred, y_true, y_base, sys, rq.off, rq.S, nb, group, P, pad, colsum + (size_t)sys * n_docs + rq.off, smem);
+}
+
+template <int SCH>
+__global__ void __launch_bounds__(1024)
+lambda_risk_model_ragged_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, const float *__restrict__ cache,
+                                int cache_stride, const float *__restrict__ ideal_colsum, int n_cached,
+                                const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries, int n_queries, int s_max,
+                                long long n_docs, int group, LambdaParams P, float pad, int lt, float *__restrict__ mat,
+                                float *__restrict__ jac) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ double red[kEffThreads / LTR_WAVE];
+    const RaggedSlot rq = ragged_slot(offsets, queries, ltr_block_id(), n_queries, s_max);
+    if (!rq.active || rq.off + rq.S > (size_t)n_docs) {      // (whole block)
+        if (rq.misfit && threadIdx.x == 0) mat[(size_t)rq.q * (1 + n_cached)] = NAN;
+        return;
+    }
+    // the rectangular kernel's cache row in two places: the entries in the query's row of `cache`, the column sums at the query's
+    // document rows of `ideal_colsum`
+    risk_model_slate<SCH>(y_pred, y_true, cache + (size_t)rq.q * cache_stride, ideal_colsum + rq.off, n_cached, rq.off, rq.S, group, P,
+                          pad, lt, mat + (size_t)rq.q * (1 + n_cached), jac, smem, red);
+}
+
+template <int SCH>
+__global__ void __launch_bounds__(1024)
+lambda_colsum_sys_bwd_ragged_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true,
+                                    const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries, int n_queries, int s_max,
+                                    long long n_docs, int group, LambdaParams P, float pad, const float *__restrict__ jac,
+                                    const float *__restrict__ coef, int coef_stride, float *__restrict__ dy_pred) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const RaggedSlot rq = ragged_slot(offsets, queries, ltr_block_id(), n_queries, s_max);
+    if (!rq.active || rq.off + rq.S > (size_t)n_docs) return;      // (whole block) a query outside the tier: its rows stay untouched
+    colsum_sys_bwd_slate<SCH>(y_pred, y_true, rq.off, rq.S, group, P, pad, jac, coef[rq.q * coef_stride], dy_pred, smem);
 }
 
 inline int check_ragged(const void *a, const void *b, const void *c, const void *offsets, int n_queries, int s_max) {
@@ -1214,6 +1284,74 @@ int ltr_lambda_ragged_fwd_bwd(const float *scores, const float *labels, const in
     if (int rc = allow_lds(lambda_ragged_kernel<SCH>, L.lds)) return rc;                                          \
     hipLaunchKernelGGL(lambda_ragged_kernel<SCH>, ltr_grid(L.grid), dim3(L.block), L.lds, (hipStream_t)stream, scores, labels, \
                        offsets, queries, n_queries, s_max, L.group, P, pad, grad_scale, slate_loss, slate_count, dscores)
+    LTR_DISPATCH_SCHEME(scheme, CALL)
+#undef CALL
+    return launch_status();
+}
+
+// group sizes of the rectangular launchers, on the tier's s_max
+static inline int colsum_fwd_group(int S) { return next_pow2(S) < 64 ? 64 : (next_pow2(S) > 1024 ? 1024 : next_pow2(S)); }
+
+int ltr_lambda_colsum_sys_ragged_fwd(const float *y_pred, const float *y_true, const float *y_base, const int64_t *offsets,
+                                     const int32_t *queries, int n_queries, int s_max, int64_t n_docs, int n_base, int scheme, int k,
+                                     float sigma, float mu, float eps, float pad, int log_base, float *colsum, void *stream) {
+    if (int rc = check_ragged(y_pred, y_true, colsum, offsets, n_queries, s_max)) return rc;
+    if (n_base > 0 && !y_base) return LTR_ERR_NULL;
+    if (n_base < 0 || n_base > 4096 || n_docs < 0) return LTR_ERR_SHAPE;
+    LambdaParams P;
+    if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
+    if (n_queries == 0) return LTR_OK;
+    const int group = colsum_fwd_group(s_max);
+    const size_t lds = (size_t)((kLambdaArrays + 1) * ((s_max + 3) & ~3) + group + 32) * sizeof(float);
+#define CALL(SCH)                                                                                                 \
+    if (int rc = allow_lds(lambda_colsum_sys_ragged_kernel<SCH>, lds)) return rc;                                 \
+    hipLaunchKernelGGL(lambda_colsum_sys_ragged_kernel<SCH>, ltr_grid((long long)(n_base + 2) * n_queries), dim3(group), lds,       \
+                       (hipStream_t)stream, y_pred, y_true, y_base, offsets, queries, n_queries, s_max, (long long)n_docs, n_base,   \
+                       group, P, pad, colsum)
+    LTR_DISPATCH_SCHEME(scheme, CALL)
+#undef CALL
+    return launch_status();
+}
+
+int ltr_lambda_risk_model_ragged_fwd(const float *y_pred, const float *y_true, const float *cache, int cache_stride,
+                                     const float *ideal_colsum, int n_cached, const int64_t *offsets, const int32_t *queries,
+                                     int n_queries, int s_max, int64_t n_docs, int scheme, int k, float sigma, float mu, float eps,
+                                     float pad, int log_base, int lt, float *mat, float *jac, void *stream) {
+    if (int rc = check_ragged(y_pred, y_true, mat, offsets, n_queries, s_max)) return rc;
+    if (!ideal_colsum || !jac || (n_cached > 0 && !cache)) return LTR_ERR_NULL;
+    if (s_max < 2 || n_cached < 0 || n_cached > 65 || cache_stride < n_cached || n_docs < 0) return LTR_ERR_SHAPE;
+    if (lt < 1 || lt > 3) return LTR_ERR_PARAM;
+    LambdaParams P;
+    if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
+    if (n_queries == 0) return LTR_OK;
+    const int group = colsum_fwd_group(s_max);                     // = ltr_lambda_risk_model_fwd's
+    const size_t lds = (size_t)((kLambdaArrays + 2) * ((s_max + 3) & ~3) + group + 32) * sizeof(float);
+#define CALL(SCH)                                                                                                 \
+    if (int rc = allow_lds(lambda_risk_model_ragged_kernel<SCH>, lds)) return rc;                                 \
+    hipLaunchKernelGGL(lambda_risk_model_ragged_kernel<SCH>, ltr_grid(n_queries), dim3(group), lds, (hipStream_t)stream, y_pred, y_true, \
+                       cache, cache_stride, ideal_colsum, n_cached, offsets, queries, n_queries, s_max, (long long)n_docs, group, P, pad, \
+                       lt, mat, jac)
+    LTR_DISPATCH_SCHEME(scheme, CALL)
+#undef CALL
+    return launch_status();
+}
+
+int ltr_lambda_colsum_sys_ragged_bwd_coef(const float *y_pred, const float *y_true, const int64_t *offsets, const int32_t *queries,
+                                          int n_queries, int s_max, int64_t n_docs, int scheme, int k, float sigma, float mu, float eps,
+                                          float pad, int log_base, const float *jac, const float *coef, int coef_stride, float *dy_pred,
+                                          void *stream) {
+    if (int rc = check_ragged(y_pred, y_true, dy_pred, offsets, n_queries, s_max)) return rc;
+    if (!jac || !coef) return LTR_ERR_NULL;
+    if (coef_stride < 1 || n_docs < 0) return LTR_ERR_SHAPE;
+    LambdaParams P;
+    if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
+    if (n_queries == 0) return LTR_OK;
+    const int group = pair_group(s_max);                           // = ltr_lambda_colsum_sys_bwd_coef's
+    const size_t lds = (size_t)((kLambdaArrays + 1) * ((s_max + 3) & ~3) + group + 32) * sizeof(float);
+#define CALL(SCH)                                                                                                 \
+    if (int rc = allow_lds(lambda_colsum_sys_bwd_ragged_kernel<SCH>, lds)) return rc;                             \
+    hipLaunchKernelGGL(lambda_colsum_sys_bwd_ragged_kernel<SCH>, ltr_grid(n_queries), dim3(group), lds, (hipStream_t)stream, y_pred,  \
+                       y_true, offsets, queries, n_queries, s_max, (long long)n_docs, group, P, pad, jac, coef, coef_stride, dy_pred)
     LTR_DISPATCH_SCHEME(scheme, CALL)
 #undef CALL
     return launch_status();

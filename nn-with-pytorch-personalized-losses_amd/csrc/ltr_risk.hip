@@ -399,21 +399,22 @@ __device__ __forceinline__ void mat_softmax(float *v, int S, double *red) {
     __syncthreads();
 }
 
-__global__ void __launch_bounds__(kMatThreads)
-risk_matrix_kernel(const float *__restrict__ ref, const float *__restrict__ x0, const float *__restrict__ rest, int B, int S, int nr,
-                   int mode, int lt, int ideal, int ones, const float *__restrict__ cached, int cache_stride, float *__restrict__ mat,
-                   float *__restrict__ jac) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ double red[kMatThreads / LTR_WAVE];
+// One query's row: b = its row of mat / cached, off = its first document row, S = its length.  Mode 1 keeps system k's column sums at
+// rest[(k - 1) * sys_stride + off ..] (sys_stride = the documents of the whole batch).  Shared by the rectangular kernel (off = b S) and
+// the ragged one: same threads, same strides, same bits.
+__device__ __forceinline__ void risk_matrix_row(const float *__restrict__ ref, const float *__restrict__ x0, const float *__restrict__ rest,
+                                                const size_t b, const size_t off, const int S, const size_t sys_stride, int nr, int mode,
+                                                int lt, int ideal, int ones, const float *__restrict__ cached, int cache_stride,
+                                                float *__restrict__ mat, float *__restrict__ jac, float *smem, double *red) {
     float *t = smem, *x = smem + S;
     // cached != NULL: columns 1 .. nr come from cached[b][0 .. nr) (the constant systems, ltr_risk_matrix_cached_fwd); only the model runs
     // ones != 0: one more column of 1.0 after the computed ones (geoRiskLambdaLoss's ideal ranking under transformation 2, :106)
-    const int b = blockIdx.x, tid = threadIdx.x, nsys = 1 + nr + (ideal && !cached ? 1 : 0), nrun = cached ? 1 : nsys;
+    const int tid = threadIdx.x, nsys = 1 + nr + (ideal && !cached ? 1 : 0), nrun = cached ? 1 : nsys;
     const int ld = nsys + (ones && !cached ? 1 : 0);
     if (cached)
-        for (int k = tid; k < nr; k += kMatThreads) mat[(size_t)b * ld + 1 + k] = cached[(size_t)b * cache_stride + k];
-    if (ld > nsys && tid == 0) mat[(size_t)b * ld + nsys] = 1.0f;
-    for (int j = tid; j < S; j += kMatThreads) t[j] = ref[(size_t)b * S + j];
+        for (int k = tid; k < nr; k += kMatThreads) mat[b * ld + 1 + k] = cached[b * cache_stride + k];
+    if (ld > nsys && tid == 0) mat[b * ld + nsys] = 1.0f;
+    for (int j = tid; j < S; j += kMatThreads) t[j] = ref[off + j];
     __syncthreads();
     if (mode != 1) mat_softmax(t, S, red);
     double nt_a = 0.0, st_a = 0.0;
@@ -428,8 +429,8 @@ risk_matrix_kernel(const float *__restrict__ ref, const float *__restrict__ x0, 
         for (int j = tid; j < S; j += kMatThreads) {
             float v;
             if (is_ideal) v = t[j];
-            else if (sys == 0) v = x0[(size_t)b * S + j];
-            else v = mode != 1 ? rest[((size_t)b * S + j) * nr + (sys - 1)] : rest[((size_t)(sys - 1) * B + b) * S + j];
+            else if (sys == 0) v = x0[off + j];
+            else v = mode != 1 ? rest[(off + j) * nr + (sys - 1)] : rest[(size_t)(sys - 1) * sys_stride + off + j];
             x[j] = v;
         }
         __syncthreads();
@@ -460,7 +461,7 @@ risk_matrix_kernel(const float *__restrict__ ref, const float *__restrict__ x0, 
         if (lt == 1) m = c;
         else if (lt == 2) m = ca / den;
         else m = mode == 1 ? (sx - st) * (sx - st) : (a - nt) * (a - nt);
-        if (tid == 0) mat[(size_t)b * ld + sys] = (float)m;
+        if (tid == 0) mat[b * ld + sys] = (float)m;
         if (sys == 0 && jac) {
             // g_j = d m / d x_j; mode 0: x = softmax(s): d m / d s_j = x_j (g_j - sum_k x_k g_k)
             // The installed torch (2.10, ATen cosine_similarity) clamps the two norms IN PLACE under no-grad: the VALUE uses
@@ -482,12 +483,63 @@ risk_matrix_kernel(const float *__restrict__ ref, const float *__restrict__ x0, 
                 double dot_a = 0.0;
                 for (int j = tid; j < S; j += kMatThreads) dot_a += (double)x[j] * grad(j);
                 const double dot = mat_block_sum(dot_a, red);
-                for (int j = tid; j < S; j += kMatThreads) jac[(size_t)b * S + j] = (float)((double)x[j] * (grad(j) - dot));
+                for (int j = tid; j < S; j += kMatThreads) jac[off + j] = (float)((double)x[j] * (grad(j) - dot));
             } else {
-                for (int j = tid; j < S; j += kMatThreads) jac[(size_t)b * S + j] = (float)grad(j);
+                for (int j = tid; j < S; j += kMatThreads) jac[off + j] = (float)grad(j);
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(kMatThreads)
+risk_matrix_kernel(const float *__restrict__ ref, const float *__restrict__ x0, const float *__restrict__ rest, int B, int S, int nr,
+                   int mode, int lt, int ideal, int ones, const float *__restrict__ cached, int cache_stride, float *__restrict__ mat,
+                   float *__restrict__ jac) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ double red[kMatThreads / LTR_WAVE];
+    const size_t b = blockIdx.x;
+    risk_matrix_row(ref, x0, rest, b, b * S, S, (size_t)B * S, nr, mode, lt, ideal, ones, cached, cache_stride, mat, jac, smem, red);
+}
+
+// The ragged batch: query q owns document rows offsets[q] .. offsets[q + 1] - 1, any lengths 1 .. s_max in ONE
+// launch -- the kernel runs 256 threads per query whatever its length, so there is no tier here.  The query id, its offset and its
+// length are wave-uniform and taken through v_readfirstlane: S and everything derived from it stay in scalar registers, as with the
+// rectangular kernel's argument.  A listed query with a length outside 1 .. s_max (the LDS is sized for s_max; the host layer never
+// lists one) gets a NaN model entry; none of its rows is read or written.
+struct MatQuery {
+    long long q, off, len;     // query id, first document row, documents
+    bool listed, fits;         // slot < n_queries; 1 <= len <= s_max and its rows inside the batch
+};
+// (no tier rule here, unlike ltr_losses.hip's ragged_slot: these kernels run the same threads for any length)
+__device__ __forceinline__ MatQuery mat_query(const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries, int n_queries,
+                                              int s_max, long long n_docs) {
+    MatQuery r = {0, 0, 0, false, false};
+    const long long slot = ltr_wave_uniform(ltr_block_id());
+    if (slot >= n_queries) return r;
+    r.listed = true;
+    r.q = ltr_wave_uniform(queries ? (long long)queries[slot] : slot);
+    r.off = ltr_wave_uniform(offsets[r.q]);
+    r.len = ltr_wave_uniform(offsets[r.q + 1]) - r.off;
+    r.fits = r.len >= 1 && r.len <= s_max && r.off >= 0 && r.off + r.len <= n_docs;
+    return r;
+}
+
+__global__ void __launch_bounds__(kMatThreads)
+risk_matrix_ragged_kernel(const float *__restrict__ ref, const float *__restrict__ x0, const float *__restrict__ rest,
+                          const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries, int n_queries, int s_max,
+                          long long n_docs, int nr, int mode, int lt, int ideal, int ones, const float *__restrict__ cached,
+                          int cache_stride, float *__restrict__ mat, float *__restrict__ jac) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ double red[kMatThreads / LTR_WAVE];
+    const MatQuery mq = mat_query(offsets, queries, n_queries, s_max, n_docs);
+    if (!mq.listed) return;                      // (whole block: the y-padding of a two-dimensional grid)
+    if (!mq.fits) {                              // (whole block)
+        const int ld = 1 + nr + (ideal && !cached ? 1 : 0) + (ones && !cached ? 1 : 0);
+        if (threadIdx.x == 0) mat[(size_t)mq.q * ld] = NAN;
+        return;
+    }
+    risk_matrix_row(ref, x0, rest, (size_t)mq.q, (size_t)mq.off, (int)mq.len, (size_t)n_docs, nr, mode, lt, ideal, ones, cached,
+                    cache_stride, mat, jac, smem, red);
 }
 
 // d loss / d x0 of a risk loss whose matrix came from risk_matrix_kernel: ds[b][j] = jac[b][j] * dmat[b][0] (the column-0 entry of
@@ -500,6 +552,18 @@ risk_scores_grad_kernel(const float *__restrict__ jac, const float *__restrict__
         const long long b = e / S;
         ds[e] = jac[e] * coef[b * coef_stride];
     }
+}
+
+// The same product on a ragged batch: one workgroup per listed query q, ds[d] = jac[d] * coef[q * coef_stride] over q's own rows
+// (q, its offset and its length through v_readfirstlane: the coefficient is one scalar load per workgroup).
+__global__ void __launch_bounds__(256)
+risk_scores_grad_ragged_kernel(const float *__restrict__ jac, const float *__restrict__ coef, int coef_stride,
+                               const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries, int n_queries, long long n_docs,
+                               float *__restrict__ ds) {
+    const MatQuery mq = mat_query(offsets, queries, n_queries, kMatMaxS, n_docs);
+    if (!mq.listed || !mq.fits) return;          // not a query of a risk batch: its rows stay untouched
+    const float c = coef[mq.q * coef_stride];
+    for (int j = threadIdx.x; j < (int)mq.len; j += 256) ds[mq.off + j] = jac[mq.off + j] * c;
 }
 
 }  // namespace
@@ -610,6 +674,30 @@ int ltr_risk_matrix_fwd(const float *ref, const float *x0, const float *rest, in
                        S, n_rest, mode, lt, ideal ? 1 : 0, 0, nullptr, 0, mat, jac);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? LTR_OK : (int)e;
+}
+
+int ltr_risk_matrix_ragged_fwd(const float *ref, const float *x0, const float *rest, const int64_t *offsets, const int32_t *queries,
+                               int n_queries, int s_max, int64_t n_docs, int n_rest, int mode, int lt, int ideal, int ones,
+                               const float *cached, int cache_stride, float *mat, float *jac, void *stream) {
+    if (!ref || !x0 || !mat || !offsets || (n_rest > 0 && !rest && !cached)) return LTR_ERR_NULL;
+    if (n_queries < 0 || s_max < 1 || s_max > kMatMaxS || n_docs < 0 || n_rest < 0 || n_rest > (cached ? 65 : 64)) return LTR_ERR_SHAPE;
+    if (cached && (cache_stride < n_rest || ideal || ones)) return LTR_ERR_SHAPE;
+    if (mode < 0 || mode > 2 || lt < 1 || lt > 3) return LTR_ERR_PARAM;
+    if (n_queries == 0) return LTR_OK;
+    hipLaunchKernelGGL(risk_matrix_ragged_kernel, ltr_grid(n_queries), dim3(kMatThreads), (size_t)2 * s_max * sizeof(float),
+                       (hipStream_t)stream, ref, x0, cached ? cached : rest, offsets, queries, n_queries, s_max, (long long)n_docs, n_rest,
+                       mode, lt, ideal ? 1 : 0, ones ? 1 : 0, cached, cache_stride, mat, jac);
+    return status();
+}
+
+int ltr_risk_scores_grad_ragged(const float *jac, const float *dmat, int dmat_stride, const int64_t *offsets, const int32_t *queries,
+                                int n_queries, int64_t n_docs, float *dscores, void *stream) {
+    if (!jac || !dmat || !dscores || !offsets) return LTR_ERR_NULL;
+    if (n_queries < 0 || n_docs < 0 || dmat_stride < 1) return LTR_ERR_SHAPE;
+    if (n_queries == 0) return LTR_OK;
+    hipLaunchKernelGGL(risk_scores_grad_ragged_kernel, ltr_grid(n_queries), dim3(256), 0, (hipStream_t)stream, jac, dmat, dmat_stride,
+                       offsets, queries, n_queries, (long long)n_docs, dscores);
+    return status();
 }
 
 }  // extern "C"

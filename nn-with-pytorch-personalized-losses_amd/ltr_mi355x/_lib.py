@@ -59,6 +59,15 @@ _PROTOTYPES = {
     "ltr_lambda_ragged_fwd_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
                                           c_float, P, P, P, P]),
     "ltr_ndcg_at_k_ragged": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    # the risk-sensitive losses on ragged batches (n_docs after s_max / n_queries)
+    "ltr_risk_matrix_ragged_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, P]),
+    "ltr_risk_scores_grad_ragged": (c_int, [P, P, c_int, P, P, c_int, c_int64, P, P]),
+    "ltr_lambda_colsum_sys_ragged_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int64, c_int, c_int, c_int, c_float, c_float, c_float,
+                                                 c_float, c_int, P, P]),
+    "ltr_lambda_risk_model_ragged_fwd": (c_int, [P, P, P, c_int, P, c_int, P, P, c_int, c_int, c_int64, c_int, c_int, c_float, c_float,
+                                                 c_float, c_float, c_int, c_int, P, P, P]),
+    "ltr_lambda_colsum_sys_ragged_bwd_coef": (c_int, [P, P, P, P, c_int, c_int, c_int64, c_int, c_int, c_float, c_float, c_float, c_float,
+                                                      c_int, P, P, c_int, P, P]),
     "ltr_svmlight_scan": (c_int, [c_char_p, P, P, P, c_int]),
     "ltr_svmlight_load": (c_int, [c_char_p, c_int64, c_int, c_int, P, P, P, c_int]),
     "ltr_gather_rows_f32": (c_int, [P, c_int64, P, c_int64, c_int64, P, P]),

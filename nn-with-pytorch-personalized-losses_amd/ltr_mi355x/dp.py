@@ -112,6 +112,31 @@ class QueryShardedTrainer:
         self.opt.step()
         return self.local.flat[-1]
 
+    def step_ragged(self, X, y, slates, global_batch=None, **extras):
+        """`step` for this rank's queries of unequal length (local_step.step_ragged: X [n_docs, F], y [n_docs], slates a
+        ltr_mi355x.ragged.RaggedSlates of the rank's own queries).  global_batch: the total QUERY count over all ranks.  The same
+        deferred-normalisation / one-all-reduce protocol as `step`, for the three listwise losses and -- with y_base= or base_cols=,
+        sharded like X -- the risk losses (their rows are gathered inside the local step)."""
+        data_dependent = getattr(self.local, "mean_kind", None) == "pairs"
+        ev = self.comm_events
+        if self.deferred and (global_batch is None or data_dependent):
+            self.local.step_ragged(X, y, slates, defer_norm=True, **extras)
+            buf = self.local.flat_ext
+        else:
+            gb = int(global_batch) if global_batch else self.global_batch_of(int(slates.n_queries), X.device)
+            self.local.step_ragged(X, y, slates, world_batch=gb, **extras)
+            buf = None
+        if self.collective:
+            if ev is not None:
+                ev[0].record()
+            dist.all_reduce(self.local.flat if buf is None else buf, op=dist.ReduceOp.SUM, group=self.group)
+            if ev is not None:
+                ev[1].record()
+        if buf is not None:
+            self.local.finish_norm()
+        self.opt.step()
+        return self.local.flat[-1]
+
 
 class ModuleShardedTrainer:
     """Query-sharded data parallelism for scorers whose backward fills `param.grad` (the `make_model` networks of

@@ -303,16 +303,18 @@ def ndcg_of_lists(true_lists, pred_lists, **kw):
 
 
 # ------------------------------------------------------------------------------------------------------- training step
-def step_ragged(ranker, X, y, slates, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False):
+def step_ragged(ranker, X, y, slates, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False, y_base=None,
+                base_cols=None):
     """FusedRanker.step_ragged: the three-launch chain (scorer forward with saved activations -> loss -> scorer backward; for the
     folded make_model ranker scores -> loss -> gradient partials) with the ragged loss launches in the middle.  Same flat
     [grads | loss | normaliser] buffer, same deferred-normalisation protocol as `step` (normaliser: the query count for approxNDCG,
-    the kept-pair count for lambdaLoss "mean")."""
+    the kept-pair count for lambdaLoss "mean").  The six risk-sensitive losses: _step_ragged_risk below."""
     from .scorer import LOSS_APPROXNDCG, LOSS_LAMBDA
     self = ranker
     if self.risk is not None:
-        raise NotImplementedError(f"{self.loss}: the risk-sensitive losses compare queries through one [queries x systems] matrix and "
-                                  "train on equal-length slates only: use the rectangular FusedRanker.step")
+        return _step_ragged_risk(self, X, y, slates, world_batch, keep1, keep2, seed, train, y_base, base_cols)
+    if y_base is not None or base_cols is not None:
+        raise TypeError(f"y_base / base_cols belong to the risk-sensitive losses, not {self.loss!r}")
     linear = not hasattr(self, "packed")
     if linear:
         self._check_trainable(train, keep1, keep2)
@@ -438,3 +440,249 @@ def _linear_chain(self, h, X, n, loss_launches):
     check(h.ltr_linear_unfold_grads(L, F, self._sizes, ln, ptrs, _ptr(self.partials), self.grid, _ptr(self.ws), _ptr(self.flat_grad),
                                     _stream()), "ltr_linear_unfold_grads")
     del ps
+
+
+# ------------------------------------------------------------------------------------------------------- risk-sensitive losses
+# The six losses of losses/riskLosses/riskLosses.py on a ragged batch.  Row q of the effectiveness matrix is
+# the row the reference computes for query q inside any batch of queries of q's own length, before the flip: every entry comes from
+# q's documents alone (softmaxes over its own slate, lambdaMask column sums in its own predicted-rank order).  The rows of all
+# queries, in query order, form one [Q, n_systems] matrix, and the reference's tail runs once on it (the whole-matrix flip, the risk
+# of column 0 and of the last column, the return strategy, `negative`) -- risk_step.run_tail, unchanged, gather included.
+def check_risk_batch(spec, slates, y_base, base_cols, min_queries=2):
+    """The host checks of a ragged risk step, from the host sizes alone (nothing here needs a device).  min_queries: 2 in one process
+    (the rectangular risk step's limit), 0 for a rank of a data-parallel step and for the per-dataset baseline columns."""
+    if y_base is None and base_cols is None:
+        raise NotImplementedError(f"{spec.name}: a risk-sensitive loss compares the model with baseline rankers: call "
+                                  "FusedRanker.step_ragged(X, y, slates, y_base=...) or (..., base_cols=baseline_columns_ragged(...))")
+    if y_base is not None and base_cols is not None:
+        raise ValueError(f"{spec.name}: pass exactly one of y_base= and base_cols=")
+    if not isinstance(slates, RaggedSlates):
+        raise TypeError(f"slates must be a RaggedSlates, got {type(slates).__name__}")
+    sizes = slates.sizes
+    if sizes.size and (sizes < 2).any():
+        q = int(np.flatnonzero(sizes < 2)[0])
+        raise ValueError(f"{spec.name}: query {q} has {int(sizes[q])} document; the risk-sensitive losses take queries of 2..{MAX_SLATE} "
+                         "documents (a softmax over one document is constant)")
+    if slates.n_queries < min_queries:
+        raise NotImplementedError(f"{spec.name}: the fused step takes batches of at least 2 queries, got {slates.n_queries}")
+
+
+def risk_baselines(spec, n_docs, y_base):
+    """y_base -> fp32 [n_docs, nb] contiguous (nb = 1 for tRisk, which takes [n_docs] or [n_docs, 1]); shapes checked."""
+    yb = y_base.detach()
+    if spec.t:
+        if yb.dim() == 2 and yb.shape[1] == 1:
+            yb = yb[:, 0]
+        if yb.dim() != 1 or int(yb.shape[0]) != n_docs:
+            raise ValueError(f"{spec.name}: y_base must be [n_docs] = [{n_docs}] (one baseline), got {tuple(y_base.shape)}")
+        yb = yb.unsqueeze(1)
+    elif yb.dim() != 2 or int(yb.shape[0]) != n_docs or not 2 <= yb.shape[1] <= 64:
+        raise ValueError(f"{spec.name}: y_base must be [n_docs, n] = [{n_docs}, 2..64], got {tuple(y_base.shape)}")
+    return yb.to(torch.float32).contiguous()
+
+
+def risk_cached(spec, slates, base_cols):
+    """base_cols = (entries [Q, C], ideal_colsum [n_docs] or None) of baseline_columns_ragged -> the same pair, fp32 with unit
+    strides; shapes checked."""
+    if not isinstance(base_cols, (tuple, list)) or len(base_cols) != 2:
+        raise ValueError(f"{spec.name}: base_cols must be the pair FusedRanker.baseline_columns_ragged returns")
+    ent, ics = base_cols
+    Q, n = slates.n_queries, slates.n_docs
+    if ent.dim() != 2 or int(ent.shape[0]) != Q:
+        raise ValueError(f"{spec.name}: base_cols[0] must be [Q, C] = [{Q}, C], got {tuple(ent.shape)}")
+    nb = int(ent.shape[1]) - int(spec.ideal) - int(spec.ones)
+    if (spec.t and nb != 1) or (not spec.t and not 2 <= nb <= 64):
+        raise ValueError(f"{spec.name}: base_cols[0] of width {ent.shape[1]} does not belong to this loss")
+    ent = ent.detach()
+    if ent.dtype != torch.float32 or not ent.is_contiguous():
+        ent = ent.to(torch.float32).contiguous()
+    if spec.lam:
+        if ics is None or ics.dim() != 1 or int(ics.shape[0]) != n:
+            raise ValueError(f"{spec.name}: base_cols[1] must be the ideal ranking's column sums [n_docs] = [{n}]")
+        ics = ics.detach().to(torch.float32).contiguous()
+    else:
+        ics = None
+    return ent, ics
+
+
+def _tier_lists(slates):
+    base = slates.order.data_ptr()
+    return [(s_max, base + 4 * a, cnt) for s_max, a, cnt in slates.tiers()]
+
+
+def risk_matrix(h, spec, slates, scores, yy, yb, cache, mat, jac):
+    """Rows [Q, 1 + n_const] of the effectiveness matrix into `mat`, d mat[:, 0] / d (scores or model column sums) into `jac`
+    [n_docs] (None: not wanted) -- risk_step.matrix on a ragged batch.  Listnet forms: one launch for the whole batch; Lambda forms:
+    the pair work per occupied tier, then (uncached) one matrix launch over the ragged column sums, which it returns."""
+    off, n, Q, s_max = slates.offsets.data_ptr(), slates.n_docs, slates.n_queries, slates.max_len
+    if cache is not None:
+        ent, ics = cache
+        n_c = int(ent.shape[1])
+        if spec.lam:
+            for t_max, q, cnt in _tier_lists(slates):
+                check(h.ltr_lambda_risk_model_ragged_fwd(_ptr(scores), _ptr(yy), _ptr(ent), n_c, _ptr(ics), n_c, off, q, cnt, t_max, n,
+                                                         *spec.largs, spec.lt, _ptr(mat), _ptr(jac), _stream()),
+                      "ltr_lambda_risk_model_ragged_fwd")
+        else:
+            check(h.ltr_risk_matrix_ragged_fwd(_ptr(yy), _ptr(scores), None, off, None, Q, s_max, n, n_c, spec.mode, spec.lt, 0, 0,
+                                               _ptr(ent), n_c, _ptr(mat), _ptr(jac), _stream()), "ltr_risk_matrix_ragged_fwd")
+        return None
+    nb = int(yb.shape[1])
+    if spec.lam:
+        cs = torch.empty((nb + 2, n), dtype=torch.float32, device=yy.device)
+        for t_max, q, cnt in _tier_lists(slates):
+            check(h.ltr_lambda_colsum_sys_ragged_fwd(_ptr(scores), _ptr(yy), _ptr(yb), off, q, cnt, t_max, n, nb, *spec.largs, _ptr(cs),
+                                                     _stream()), "ltr_lambda_colsum_sys_ragged_fwd")
+        check(h.ltr_risk_matrix_ragged_fwd(_ptr(cs[nb + 1]), _ptr(cs[0]), _ptr(cs[1:nb + 1]), off, None, Q, s_max, n, nb, 1, spec.lt,
+                                           int(spec.ideal), int(spec.ones), None, 0, _ptr(mat), _ptr(jac), _stream()),
+              "ltr_risk_matrix_ragged_fwd")
+        return cs
+    check(h.ltr_risk_matrix_ragged_fwd(_ptr(yy), _ptr(scores), _ptr(yb), off, None, Q, s_max, n, nb, spec.mode, spec.lt, int(spec.ideal),
+                                       0, None, 0, _ptr(mat), _ptr(jac), _stream()), "ltr_risk_matrix_ragged_fwd")
+    return None
+
+
+def risk_scores_grad(h, spec, slates, scores, yy, jac, coef_ptr, nsys, ds):
+    """d value / d scores from the model column of d value / d mat (read in place at row stride nsys): risk_step.scores_grad."""
+    off, n = slates.offsets.data_ptr(), slates.n_docs
+    if spec.lam:
+        for t_max, q, cnt in _tier_lists(slates):
+            check(h.ltr_lambda_colsum_sys_ragged_bwd_coef(_ptr(scores), _ptr(yy), off, q, cnt, t_max, n, *spec.largs, _ptr(jac), coef_ptr,
+                                                          nsys, _ptr(ds), _stream()), "ltr_lambda_colsum_sys_ragged_bwd_coef")
+    else:
+        check(h.ltr_risk_scores_grad_ragged(_ptr(jac), coef_ptr, nsys, off, None, slates.n_queries, n, _ptr(ds), _stream()),
+              "ltr_risk_scores_grad_ragged")
+
+
+def baseline_columns(spec, slates, yy, yb):
+    """(entries [Q, C], ideal_colsum [n_docs] or None): the constant part of the matrix, by the same launches as the uncached step
+    (the model's slot runs on the labels and is dropped), so the cached step's matrix is bitwise the uncached one."""
+    Q = slates.n_queries
+    mat = torch.empty((Q, 1 + spec.n_const(int(yb.shape[1]))), dtype=torch.float32, device=yy.device)
+    cs = risk_matrix(lib(), spec, slates, yy, yy, yb, None, mat, None)
+    return mat[:, 1:].contiguous(), (cs[-1].clone() if cs is not None else None)
+
+
+def _step_ragged_risk(self, X, y, slates, world_batch, keep1, keep2, seed, train, y_base, base_cols):
+    """FusedRanker.step_ragged for a risk loss: scorer forward with saved activations -> matrix rows + jac -> [all_gather] -> tail ->
+    scores gradient -> scorer backward -> reduce: FusedRanker._step_risk / LinearFusedRanker._step_risk's chain on [n_docs, F] rows."""
+    from . import risk_step as RS
+    R = self.risk
+    check_risk_batch(R, slates, y_base, base_cols, 2 if self.risk_world <= 1 else 0)
+    linear = not hasattr(self, "packed")
+    if linear:
+        self._check_trainable(train, keep1, keep2)
+    info = self.info
+    require_device(X, y)
+    slates = _slates_on(slates, X.device)
+    n, Q = slates.n_docs, slates.n_queries
+    if X.dim() != 2 or X.shape[1] != info.F or int(X.shape[0]) != n:
+        raise ValueError(f"expected X [n_docs = {n}, {info.F}], got {tuple(X.shape)}")
+    y1 = _flat(y, "y", n)
+    yb = cache = None
+    if base_cols is not None:
+        require_device(*[t for t in base_cols if torch.is_tensor(t)])
+        cache = risk_cached(R, slates, base_cols)
+        nsys = 1 + int(cache[0].shape[1])
+    else:
+        require_device(y_base)
+        yb = risk_baselines(R, n, y_base)
+        nsys = 1 + R.n_const(int(yb.shape[1]))
+    h = lib()
+    n_par = info.n_params
+    dp = (self.risk_group, self.risk_rank, self.risk_world)
+    with torch.cuda.device(self.device):
+        yy = y1.detach().to(torch.float32).contiguous()
+        mat, send, bmax = RS.matrix_rows(R, self.device, dp, Q, nsys, world_batch)
+        slot = self.flat[n_par:n_par + 1]
+
+        def loss_launches(scores, ds):
+            jac = torch.empty(n, dtype=torch.float32, device=self.device)
+            risk_matrix(h, R, slates, scores, yy, yb, cache, mat, jac)
+            coef, _dmat = RS.run_tail(h, R, dp, slot, mat, send, bmax, Q, nsys)
+            risk_scores_grad(h, R, slates, scores, yy, jac, coef, nsys, ds)
+
+        if Q == 0:                                   # a rank without queries still joins the gather and runs the tail
+            RS.run_tail(h, R, dp, slot, mat, send, bmax, Q, nsys)
+            self.flat_grad.zero_()
+        elif linear:
+            _linear_chain(self, h, X, n, loss_launches)
+        else:
+            _mlp_chain(self, h, X, n, keep1, keep2, seed, train, loss_launches)
+    self._bind_grads()
+    return self._loss_out
+
+
+@functools.lru_cache(maxsize=None)
+def _ragged_risk_loss():
+    """The autograd node of the six ragged risk losses, built on first use like _ragged_loss (tests/test_autograd_state_cpu.py pairs
+    every module-level Function with a table entry; this node's state test is tests/test_ragged_risk_gpu.py::
+    test_risk_loss_backward_uses_forward_time_state).  Its backward reads nothing but the gradient the forward launches saved."""
+    class _RaggedRiskLoss(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, scores, labels, baselines, slates, spec):
+            from . import risk_step as RS
+            check_risk_batch(spec, slates, baselines, None)
+            require_device(scores, labels, baselines)
+            slates = _slates_on(slates, scores.device)
+            n, Q = slates.n_docs, slates.n_queries
+            s_in, y_in = _flat(scores, "y_predicted", n), _flat(labels, "y_true", n)
+            ctx.in_dtype, ctx.in_shape = scores.dtype, scores.shape
+            dev = scores.device
+            h = lib()
+            with torch.cuda.device(dev):
+                s, yy = _f32(s_in), _f32(y_in)
+                yb = risk_baselines(spec, n, baselines)
+                nsys = 1 + spec.n_const(int(yb.shape[1]))
+                mat = torch.empty((Q, nsys), dtype=torch.float32, device=dev)
+                value = torch.empty(1, dtype=torch.float32, device=dev)
+                jac = ds = dmat = None
+                if ctx.needs_input_grad[0]:          # an evaluation call runs the matrix and the tail's value alone
+                    jac, ds = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+                    dmat = torch.empty((Q, nsys), dtype=torch.float32, device=dev)
+                risk_matrix(h, spec, slates, s, yy, yb, None, mat, jac)
+                RS.tail(h, spec, mat, Q, nsys, value, dmat)
+                if ds is not None:
+                    risk_scores_grad(h, spec, slates, s, yy, jac, dmat.data_ptr(), nsys, ds)
+            ctx.save_for_backward(ds)
+            return value.to(torch.result_type(scores, labels))
+
+        @staticmethod
+        def backward(ctx, go):
+            (ds,) = ctx.saved_tensors
+            if ds is None:
+                return None, None, None, None, None
+            return (ds * go.to(torch.float32)).to(ctx.in_dtype).reshape(ctx.in_shape), None, None, None, None
+    return _RaggedRiskLoss
+
+
+def risk_loss(name, y_predicted, y_true, slates, y_baselines, **risk_args):
+    """One of the six risk-sensitive losses (losses/riskLosses/riskLosses.py: name(y_predicted, y_true, y_baselines, **risk_args)) on a
+    ragged batch: y_predicted / y_true [n_docs], y_baselines [n_docs, n] (tRisk: [n_docs] or [n_docs, 1]).  Shape [1], like the
+    reference's; one autograd node, gradient to the scores only."""
+    from .risk_step import RiskSpec
+    return _ragged_risk_loss().apply(y_predicted, y_true, y_baselines, slates, RiskSpec(name, risk_args))
+
+
+def geoRiskListnetLoss(y_predicted, y_true, slates, y_baselines, **risk_args):
+    return risk_loss("geoRiskListnetLoss", y_predicted, y_true, slates, y_baselines, **risk_args)
+
+
+def geoRiskLambdaLoss(y_predicted, y_true, slates, y_baselines, **risk_args):
+    return risk_loss("geoRiskLambdaLoss", y_predicted, y_true, slates, y_baselines, **risk_args)
+
+
+def zRiskListnetLoss(y_predicted, y_true, slates, y_baselines, **risk_args):
+    return risk_loss("zRiskListnetLoss", y_predicted, y_true, slates, y_baselines, **risk_args)
+
+
+def zRiskLambdaLoss(y_predicted, y_true, slates, y_baselines, **risk_args):
+    return risk_loss("zRiskLambdaLoss", y_predicted, y_true, slates, y_baselines, **risk_args)
+
+
+def tRiskListnetLoss(y_predicted, y_true, slates, y_baselines, **risk_args):
+    return risk_loss("tRiskListnetLoss", y_predicted, y_true, slates, y_baselines, **risk_args)
+
+
+def tRiskLambdaLoss(y_predicted, y_true, slates, y_baselines, **risk_args):
+    return risk_loss("tRiskLambdaLoss", y_predicted, y_true, slates, y_baselines, **risk_args)

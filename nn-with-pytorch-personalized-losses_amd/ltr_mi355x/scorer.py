@@ -555,13 +555,32 @@ class FusedRanker:
         self._bind_grads()
         return self._loss_out
 
-    def step_ragged(self, X, y, slates, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False):
+    def step_ragged(self, X, y, slates, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False, y_base=None,
+                    base_cols=None):
         """`step` for queries of unequal length, no padding: X [n_docs, F], y [n_docs], slates a ltr_mi355x.ragged.RaggedSlates
         (query q owns rows offsets[q] .. offsets[q + 1] - 1).  The three-launch chain with one loss launch per occupied length tier;
         buffers, return value, `world_batch` (here: the global QUERY count) and defer_norm / finish_norm as in `step`.  Explicit
-        masks are [n_docs, H].  approxNDCG, ListNet and lambdaLoss; the risk-sensitive losses raise NotImplementedError."""
+        masks are [n_docs, H].  Risk losses: y_base [n_docs, n] ([n_docs] for tRisk) or base_cols (baseline_columns_ragged) -- one of
+        them is required (neither: NotImplementedError); queries of 2..2048 documents, at least 2 of them in one process."""
         from .ragged import step_ragged
-        return step_ragged(self, X, y, slates, world_batch, keep1, keep2, seed, train, defer_norm)
+        return step_ragged(self, X, y, slates, world_batch, keep1, keep2, seed, train, defer_norm, y_base, base_cols)
+
+    def baseline_columns_ragged(self, y, y_base, slates):
+        """The constant part of a risk loss's matrix for the queries of `slates`: (entries [Q, C], ideal_colsum [n_docs] or None --
+        the ideal ranking's column sums, Lambda forms only), to pass as step_ragged(..., base_cols=(entries, ideal_colsum)).  Computed
+        by the launches of the uncached step: the matrix is bitwise the same.  For a batch of consecutive queries q0 .. q1 - 1 slice
+        entries[q0:q1] and ideal_colsum[d0:d1] (slates.doc_range); for slates.permuted(perm) -> (new, doc_index) pass
+        (entries[perm], gather_rows(ideal_colsum[:, None], doc_index)[:, 0])."""
+        from . import ragged
+        if self.risk is None:
+            raise TypeError(f"baseline_columns_ragged belongs to the risk-sensitive losses, not {self.loss!r}")
+        ragged.check_risk_batch(self.risk, slates, y_base, None, min_queries=0)
+        require_device(y, y_base)
+        slates = ragged._slates_on(slates, y.device)
+        n = slates.n_docs
+        with torch.cuda.device(y.device):
+            yy = ragged._flat(y, "y", n).detach().to(torch.float32).contiguous()
+            return ragged.baseline_columns(self.risk, slates, yy, ragged.risk_baselines(self.risk, n, y_base))
 
     def _reduce(self, fold, pf, partials, grid):
         """Per-workgroup partials -> the flat gradient of the module's own tensors (through the unfold for a folded TripleLayerNet)."""
