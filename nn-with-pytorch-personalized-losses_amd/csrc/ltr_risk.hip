@@ -175,7 +175,7 @@ __device__ __forceinline__ RowBlocks row_blocks(int n_blocks, int block_rows, in
 }
 
 // The TAIL of a tRisk loss in one launch (riskLosses.py:269-291 / :332-345) on the [Q][2] matrix (model, baseline): the flip of
-// transformation 1 (mat' = -mat + max(mat), in the reference's fp32 arithmetic), the alpha-weighted deltas, mean / std, the
+// transformation 1 (mat' = -mat + max(mat), exact in fp64), the alpha-weighted deltas, mean / std, the
 // `negative` factor; value and d value / d mat together.  The flip's whole-matrix maximum gets no gradient: the gradients of the
 // two columns of a query are g and -g, so their sum over the matrix is zero.
 __global__ void __launch_bounds__(kRiskThreads)
@@ -199,17 +199,17 @@ trisk_tail_kernel(const float *__restrict__ mat, int n_blocks, int block_rows, i
         for (int w = 1; w < kRiskThreads / LTR_WAVE; ++w) M = fmaxf(M, (float)red[w]);
         __syncthreads();
     }
-    auto at = [&](int q, int j) -> float { return flip ? -mat[rb.row(q) + j] + M : mat[rb.row(q) + j]; };
+    auto at = [&](int q, int j) -> double { const double x = (double)mat[rb.row(q) + j]; return flip ? (double)M - x : x; };   // exact
     double s = 0.0;
     for (int q = tid; q < Q; q += kRiskThreads) {
-        const float a = at(q, 0), b = at(q, 1);
-        s += ((double)a - (double)b) * (a < b ? 1.0 + (double)alpha : 1.0);
+        const double a = at(q, 0), b = at(q, 1);
+        s += (a - b) * (a < b ? 1.0 + (double)alpha : 1.0);
     }
     const double mu = block_sum_f64(s, red) / (double)Q;
     double v = 0.0;
     for (int q = tid; q < Q; q += kRiskThreads) {
-        const float a = at(q, 0), b = at(q, 1);
-        const double x = ((double)a - (double)b) * (a < b ? 1.0 + (double)alpha : 1.0);
+        const double a = at(q, 0), b = at(q, 1);
+        const double x = (a - b) * (a < b ? 1.0 + (double)alpha : 1.0);
         v += (x - mu) * (x - mu);
     }
     const double var = block_sum_f64(v, red) / (double)(Q - 1);
@@ -217,9 +217,9 @@ trisk_tail_kernel(const float *__restrict__ mat, int n_blocks, int block_rows, i
     if (tid == 0) value[0] = (float)(mu / se) * factor;
     if (!dmat) return;
     for (int q = tid; q < Q; q += kRiskThreads) {
-        const float a = at(q, 0), b = at(q, 1);
+        const double a = at(q, 0), b = at(q, 1);
         const double c = a < b ? 1.0 + (double)alpha : 1.0;
-        const double x = ((double)a - (double)b) * c;
+        const double x = (a - b) * c;
         const float g = (float)((1.0 / ((double)Q * se) - mu * (x - mu) / ((double)(Q - 1) * se * var)) * c) * factor;
         const size_t r = rb.row(q);
         dmat[r] = flip ? -g : g;
@@ -264,8 +264,9 @@ risk_tail_kernel(const float *__restrict__ mat, int n_blocks, int block_rows, in
         for (int w = 1; w < kRiskThreads / LTR_WAVE; ++w) M = fmax(M, red[w]);
         M = (double)(float)M;
     }
-    // the flipped entry in the reference's fp32 arithmetic (-mat + max), then promoted
-    auto at = [&](int q, int j) -> double { return flip ? (double)(-mat[rb.row(q) + j] + (float)M) : (double)mat[rb.row(q) + j]; };
+    // the flipped entry -mat + max, exact in fp64 (both operands are fp32 numbers).  Rounding it to fp32 first, as the reference's
+    // tensors do, moved zRisk at alpha = 0 (a cancelling sum of residuals) by 5.8e-5 on a 3 x 9 matrix: tests/test_risk_tails_gpu.py
+    auto at = [&](int q, int j) -> double { const double x = (double)mat[rb.row(q) + j]; return flip ? M - x : x; };
     const int ncol = strategy == 1 ? 1 : 2;
     const int cols[2] = {0, n - 1};
     RiskCol rc[2];

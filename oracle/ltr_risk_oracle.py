@@ -88,8 +88,9 @@ def pair_colsum(p, p_true, scheme, k=None, sigma=1.0, pad=-1, reduction_log="bin
     return full.sum(dim=1)
 
 
-def listnet_matrix(p_true, p_pred, p_base, lt, add_ideal):
-    """riskLosses.py:16-49 (= :136-169).  Systems: model, baselines..., [ideal]."""
+def listnet_matrix(p_true, p_pred, p_base, lt, add_ideal, flip=True):
+    """riskLosses.py:16-49 (= :136-169).  Systems: model, baselines..., [ideal].  flip=False: the matrix before the final
+    `-mat + max(mat)` of transformations 1 / 3 (what ltr_risk_matrix_fwd writes; risk_tail(flip=True) applies the flip)."""
     systems = [p_pred] + ([] if p_base is None else [p_base[:, :, j] for j in range(p_base.shape[2])])
     if add_ideal == 2:
         systems.append(p_true)
@@ -101,11 +102,11 @@ def listnet_matrix(p_true, p_pred, p_base, lt, add_ideal):
         ref = (p_true * p_true).sum(dim=1)
         cols = [((p_true * p).sum(dim=1) - ref) ** 2 for p in systems]
     mat = torch.stack(cols, dim=1)
-    return mat.max() - mat if lt in (1, 3) else mat
+    return mat.max() - mat if flip and lt in (1, 3) else mat
 
 
-def lambda_matrix(p_true, p_pred, p_base, lt, add_ideal, scheme, ideal_ones):
-    """riskLosses.py:71-117 (geo) / :191-236 (z)."""
+def lambda_matrix(p_true, p_pred, p_base, lt, add_ideal, scheme, ideal_ones, flip=True):
+    """riskLosses.py:71-117 (geo) / :191-236 (z).  flip=False: before the final `-mat + max(mat)` of transformation 1."""
     tt = pair_colsum(p_true, p_true, scheme)
     systems = [pair_colsum(p_pred, p_true, scheme)]
     if p_base is not None:
@@ -119,7 +120,7 @@ def lambda_matrix(p_true, p_pred, p_base, lt, add_ideal, scheme, ideal_ones):
         if add_ideal == 2:
             cols.append(torch.ones(tt.shape[0], dtype=torch.float) if ideal_ones else _cos(tt, tt))
     mat = torch.stack(cols, dim=1)
-    return mat.max() - mat if lt == 1 else mat
+    return mat.max() - mat if flip and lt == 1 else mat
 
 
 def _strategy(fn, mat, alpha, rs):
@@ -152,10 +153,10 @@ def z_risk_lambda(y_pred, y_true, y_base=None, alpha=5, lt=1, rs=1, negative=1, 
     return (negative * _strategy(z_risk, lambda_matrix(pt, pp, pb, lt, add_ideal, scheme, False), alpha, rs)).reshape(1)
 
 
-def _t_cols(q_true, q_pred, q_base, lt):
+def _t_cols(q_true, q_pred, q_base, lt, flip=True):
     if lt == 1:
         m = torch.stack([((q_pred - q_true) ** 2).sum(dim=1), ((q_base - q_true) ** 2).sum(dim=1)])
-        return m.max() - m
+        return m.max() - m if flip else m
     if lt == 2:
         return torch.stack([_cos(q_true, q_pred), _cos(q_true, q_base)])
     ref = q_true.sum(dim=1)
@@ -172,3 +173,33 @@ def t_risk_lambda(y_pred, y_true, y_base, alpha=5, lt=1, negative=1, scheme="ndc
     pt, pp, pb = _softmaxes(y_pred, y_true, y_base)
     m = _t_cols(pair_colsum(pt, pt, scheme), pair_colsum(pp, pt, scheme), pair_colsum(pb, pt, scheme), lt)
     return (negative * t_risk_tail(m[0], m[1], alpha)).reshape(1)
+
+
+# ------------------------------------------------------------------------------------------------- the two tails
+# What ltr_risk_tail_fwd_bwd / ltr_trisk_tail_fwd_bwd (include/ltr_mi355x.h) compute from the UNFLIPPED matrix, restated with the
+# functions above; dtype-generic, autograd through every step (torch's whole-tensor max hands its gradient to the maximal entries,
+# evenly among ties).  The six losses above are these tails on their matrices (tests/test_risk_tails_cpu.py holds them to that).
+def risk_tail_parts(mat, alpha, geo, strategy, flip, factor, zquirk=False):
+    """(value [1], R0, R1): R0 / R1 = risk of column 0 / of the last column (R1 None under strategy 1)."""
+    m = -mat + mat.max() if flip else mat
+    fn = geo_risk if geo else z_risk
+    r0 = fn(m, alpha, 0).reshape(1)
+    if strategy == 1:
+        return factor * r0, r0, None
+    r1 = fn(m, alpha, -1).reshape(1)
+    if strategy == 2:
+        return (factor * r1 - r0 if zquirk else factor * (r1 - r0)), r0, r1
+    if strategy == 3:
+        return factor * (r1 - r0) ** 2, r0, r1
+    raise ValueError(f"return strategy {strategy!r}")
+
+
+def risk_tail(mat, alpha, geo, strategy, flip, factor, zquirk=False):
+    """mat [Q, n] -> [1]: strategy 1: f R0, 2: f (R1 - R0) [zquirk: f R1 - R0, riskLosses.py:176], 3: f (R1 - R0)^2."""
+    return risk_tail_parts(mat, alpha, geo, strategy, flip, factor, zquirk)[0]
+
+
+def t_risk_pair_tail(mat, alpha, flip, factor):
+    """mat [Q, 2] = (model, baseline) per query -> [1]: factor * mean / std of the alpha-weighted deltas (riskLosses.py:269-291)."""
+    m = -mat + mat.max() if flip else mat
+    return (factor * t_risk_tail(m[:, 0], m[:, 1], alpha)).reshape(1)

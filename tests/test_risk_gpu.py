@@ -201,7 +201,9 @@ def test_fused_risk_matrix_cosine_of_a_zero_vector(ideal, dev):
 def test_fused_risk_tail_matches_the_tensor_algebra_path(Q, n, kind, strategy, flip, dev):
     """ltr_risk_tail_fwd_bwd (flip + risk of column 0 and of the last column + return strategy + `negative` in one launch) against
     the same tail through torch ops and the per-column risk kernels (an fp64 matrix takes that path), value and gradient, incl. the
-    reference's precedence quirk of zRiskListnetLoss and the max's gradient under the flip."""
+    reference's precedence quirk of zRiskListnetLoss and the max's gradient under the flip.  The fp64 side runs the per-column kernels
+    (ltr_risk_fwd_bwd, same formulas, same file), so this pins the module path's routing; the independent gate of the tail kernels
+    against the fp64 oracle is tests/test_risk_tails_gpu.py."""
     from losses.riskLosses import riskLosses as RL
     from ltr_mi355x import risk as R
     gen = torch.Generator().manual_seed(Q * 10 + n + strategy)
@@ -231,7 +233,8 @@ def test_fused_risk_tail_matches_the_tensor_algebra_path(Q, n, kind, strategy, f
 def test_trisk_pair_through_the_fused_matrix(B, S, lt, fn, dev):
     """The tRisk pair takes its [queries, 2] matrix from ltr_risk_matrix_fwd (mode 2: the Listnet flavour's cosine is taken between
     the PRODUCTS t^2 and t p; mode 1 for the column sums of the Lambda flavour): fp32 inputs (fused) against fp64 inputs (the
-    tensor-algebra path), value and gradient."""
+    tensor-algebra path), value and gradient.  The fp64 side runs the per-column kernel ltr_trisk_fwd_bwd, so this pins the module
+    path's routing; the independent gate against the fp64 oracle is tests/test_risk_tails_gpu.py."""
     from losses.riskLosses import riskLosses as RL
     gen = torch.Generator().manual_seed(B * 100 + S + lt)
     yp, yt, yb = torch.randn(B, S, generator=gen), torch.randint(0, 5, (B, S), generator=gen).float(), torch.randn(B, S, generator=gen)
