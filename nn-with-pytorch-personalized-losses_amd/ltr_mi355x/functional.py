@@ -238,7 +238,10 @@ class Ordinal(torch.autograd.Function):
                                             _ptr(dp), _stream()), "ltr_ordinal_fwd_bwd")
             loss = sums[0] / sums[1]
             if dp is not None:
-                dp = dp / sums[1]
+                # no valid document: the loss is 0 / 0, but every entry is masked and the reference zeroes masked entries BEFORE
+                # it divides (ordinal.py:45), so their gradient is 0 there too, not 0 / 0
+                # (the count is a non-negative integer: clamping it at 1 changes nothing else)
+                dp = dp / sums[1].clamp(min=1.0)
         ctx.save_for_backward(dp)
         return loss.to(y_pred.dtype)
 

@@ -12,17 +12,39 @@ import math
 import numpy as np
 
 
-def ranks_desc(v, stable=True):
-    """0-based rank of every entry of each row under a descending sort.
-    stable=True : ties keep index order -- Python's sorted(..., reverse=True) (metrics.py:51, the default path).
-    stable=False: ties in REVERSE index order -- np.argsort(v)[::-1] when argsort is stable (metrics.py:53); numpy's
-                  default sort kind is not guaranteed stable, so that path is only pinned on tie-free data."""
+SORT_ABOVE = 512        # ranks_desc: the [Q, S, S] counting cube up to here (8 S^2 bytes a query), the sort-based form beyond
+
+
+def ranks_desc_counting(v, stable=True):
+    """ranks_desc by counting: rank_i = #{j : v_j beats i}.  A [Q, S, S] boolean cube: small S only."""
     v = np.asarray(v, dtype=np.float64)
     gt = v[:, None, :] > v[:, :, None]                       # [q, i, j]: j beats i
     idx = np.arange(v.shape[1])
     tie = (v[:, None, :] == v[:, :, None]) & ((idx[None, None, :] < idx[None, :, None]) if stable
                                               else (idx[None, None, :] > idx[None, :, None]))
     return (gt | tie).sum(axis=2)
+
+
+def ranks_desc_sorting(v, stable=True):
+    """ranks_desc by sorting: np.lexsort on (-v, +index) or (-v, -index), then the inverse permutation.  O(S log S) a query and no
+    cube, so S = 16384 costs nothing; equal to the counting form on any NaN-free input (+0.0 and -0.0 compare equal in both)."""
+    v = np.asarray(v, dtype=np.float64)
+    Q, S = v.shape
+    idx = np.broadcast_to(np.arange(S), (Q, S))
+    order = np.lexsort((idx if stable else -idx, -v), axis=1)        # last key is the primary one
+    r = np.empty((Q, S), dtype=np.int64)
+    np.put_along_axis(r, order, idx, axis=1)
+    return r
+
+
+def ranks_desc(v, stable=True):
+    """0-based rank of every entry of each row under a descending sort.
+    stable=True : ties keep index order -- Python's sorted(..., reverse=True) (metrics.py:51, the default path).
+    stable=False: ties in REVERSE index order -- np.argsort(v)[::-1] when argsort is stable (metrics.py:53); numpy's
+                  default sort kind is not guaranteed stable, so that path is only pinned on tie-free data.
+    Counting up to SORT_ABOVE documents, sorting beyond; tests/test_eval_edges_cpu.py holds the two forms equal."""
+    v = np.asarray(v, dtype=np.float64)
+    return ranks_desc_counting(v, stable) if v.shape[1] <= SORT_ABOVE else ranks_desc_sorting(v, stable)
 
 
 def dcg_at_k(y_true, order_key, k, gains, stable=True):
@@ -39,7 +61,8 @@ def dcg_at_k(y_true, order_key, k, gains, stable=True):
 
 
 def ndcg_per_query(y_true, y_score, k=5, no_relevant=True, gains="linear", stable=True):
-    """metrics.py:67-78: per-query NDCG@k; a query with ideal DCG 0 scores 1.0 (no_relevant) or 0.0."""
+    """metrics.py:67-78: per-query NDCG@k; a query with ideal DCG 0 scores 1.0 (no_relevant) or 0.0.  Any other ideal DCG divides,
+    a negative one included (linear gains on negative labels): metrics.py:72-74 tests `== 0` and nothing else."""
     d = dcg_at_k(y_true, y_score, k, gains, stable)
     ideal = dcg_at_k(y_true, y_true, k, gains, stable)
     out = np.where(ideal == 0.0, 1.0 if no_relevant else 0.0, d / np.where(ideal == 0.0, 1.0, ideal))

@@ -325,16 +325,20 @@ def ordinal(y_pred, y_true, n, pad=-1):
 
 
 def ordinal_closed_form(y_pred, y_true, n, pad=-1):
-    """(loss, dL/dy_pred): BCE backward as ATen does it, (p - t) / max((1-p) p, 1e-12), / #valid docs."""
+    """(loss, dL/dy_pred) in y_pred's dtype (fp64 in, fp64 throughout): BCE backward as ATen does it,
+    (p - t) / max((1-p) p, 1e-12), / #valid docs.  The targets carry the DEFAULT indicator -1 whatever `pad` is and the mask
+    compares with `pad` (ordinal.py:39-41), so pad = 0 / 1 masks TARGETS and leaves a padded document's -1 targets in the loss,
+    through ATen's formula, which is affine in t.  No valid document: the loss is 0 / 0 = NaN (no exception) and the gradient 0
+    everywhere -- the reference zeroes masked entries before the division (`ls[mask] = 0.0`, :45), so nothing flows back to them."""
     with torch.no_grad():
-        t = with_ordinals(y_true, n)
+        t = with_ordinals(y_true, n).to(y_pred.dtype)
         masked = t == pad
         logp = torch.log(y_pred).clamp(min=-100.0)
         log1p = torch.log(1.0 - y_pred).clamp(min=-100.0)
         ls = torch.where(masked, torch.zeros_like(y_pred), -(t * logp + (1.0 - t) * log1p))
         n_docs = ((~masked).sum(2) > 0).sum().to(y_pred.dtype)
         g = (y_pred - t) / ((1.0 - y_pred) * y_pred).clamp(min=1e-12)
-        g = torch.where(masked, torch.zeros_like(g), g) / n_docs
+        g = torch.where(masked, torch.zeros_like(g), g / n_docs)
         return ls.sum() / n_docs, g
 
 
