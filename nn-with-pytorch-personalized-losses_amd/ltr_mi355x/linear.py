@@ -21,12 +21,13 @@ Listnet forms with S in {32, 64, 128}: fold -> ltr_linear_risk_rows (X read ONCE
 ltr_linear_scores -> risk_step.matrix -> [all_gather] -> tail -> risk_step.scores_grad -> ltr_linear_grad_partials -> unfold.
 """
 import ctypes
+from types import SimpleNamespace
 
 import torch
 
 from ._lib import check, lib
 from .functional import _ptr, _stream, require_device
-from .scorer import LOSS_APPROXNDCG, LOSS_LAMBDA, LOSS_LISTNET, LOSS_RISK, FusedRanker, cu_count
+from .scorer import LOSS_LAMBDA, FusedRanker, cu_count
 
 MAX_LAYERS = 16
 MAX_FEATURES = 1024
@@ -69,65 +70,29 @@ class LinearFusedRanker(FusedRanker):
 
     def __init__(self, module, loss="approxNDCG", alpha=1.0, eps=1e-10, padded_value_indicator=-1, apply_sigmoid=False, grid=None,
                  weighing_scheme=None, k=None, sigma=1.0, mu=10.0, reduction="sum", reduction_log="binary", risk_args=None):
-        if loss not in self.LOSSES:
-            raise KeyError(f"fused loss must be one of {sorted(self.LOSSES)}, got {loss!r}")
-        self.risk = None
-        if self.LOSSES[loss] == LOSS_RISK:
-            from .risk_step import RiskSpec
-            self.risk = RiskSpec(loss, risk_args)          # option errors first: they need no device
-            # data parallel: ltr_mi355x.dp.QueryShardedTrainer sets (group, rank, world) -- the risk step all-gathers its matrix rows
-            self.risk_group = None
-            self.risk_rank, self.risk_world = 0, 1
-        elif risk_args is not None:
-            raise TypeError(f"risk_args belongs to the risk-sensitive losses, not {loss!r}")
+        self._init_risk(loss, risk_args)
         F, sizes, ln, self._dropout = linear_shape(module)
         if len(sizes) > MAX_LAYERS:
             raise ValueError(f"at most {MAX_LAYERS} FC layers fold, got {len(sizes)}")
         if F > MAX_FEATURES:
             raise ValueError(f"at most {MAX_FEATURES} input features, got {F}")
         self.module = module
-        self.loss = loss
-        self.loss_kind = self.LOSSES[loss]
-        self.alpha, self.eps, self.pad = float(alpha), float(eps), float(padded_value_indicator)
-        self.apply_sigmoid = bool(apply_sigmoid)
-        self.lambda_args = (4, 0, 1.0, 10.0, 1e-10, -1.0, 0)
-        if self.loss_kind == LOSS_LAMBDA:
-            from .functional import _lambda_args
-            if reduction not in ("sum", "mean"):
-                raise ValueError("Reduction method can be either sum or mean")
-            self.lambda_args = _lambda_args(eps, padded_value_indicator, weighing_scheme, k, sigma, mu, reduction_log)
-        self.reduction = reduction
+        self._init_loss(loss, alpha, eps, padded_value_indicator, apply_sigmoid, weighing_scheme, k, sigma, mu, reduction, reduction_log)
         self.params = module._ltr_params()
         require_device(*self.params)
         self.info = _Info(F, sizes, ln, sum(p.numel() for p in self.params))
-        dev = self.params[0].device
-        self.device = dev
+        dev = self.device = self.params[0].device
         h = lib()
         self.grid = int(grid) if grid else int(h.ltr_linear_grid(cu_count(dev)))
-        self.flat_ext = torch.zeros(self.info.n_params + 2, dtype=torch.float32, device=dev)
-        self.flat = self.flat_ext[:self.info.n_params + 1]
-        self.flat_grad = self.flat[:self.info.n_params]
-        self._norm = self.flat_ext[self.info.n_params + 1:]
-        self._grad_views = []
-        off = 0
-        for p in self.params:
-            self._grad_views.append(self.flat_grad[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        self._bind_grads()
+        self._init_flat()
         self._sizes = (ctypes.c_int * max(1, len(sizes)))(*sizes)
         nws = int(h.ltr_linear_ws_doubles(len(sizes), F, self._sizes))
         check(-2 if nws < 0 else 0, "ltr_linear_ws_doubles")
         self.ws = torch.empty(nws, dtype=torch.float64, device=dev)         # fold -> unfold of ONE step; rewritten every step
         self.weff = torch.empty(F + 2, dtype=torch.float32, device=dev)
         self.partials = torch.empty(self.grid * (F + 1), dtype=torch.float32, device=dev)
-        self._loss_out = self.flat[self.info.n_params]
-        self._slate = None
-        self._bufs = None              # scores / ds / stats of the multi-launch path (grown on demand)
+        self._bufs = None              # scores / ds / stats of the chain (grown on demand)
         self._rows = None              # R [B][F + 1] of the one-pass risk step (grown on demand)
-        self._jac = None               # d mat[:, 0] / d scores of the risk chain (grown on demand)
-        self._calls = 0
-        self.seed_salt = 0
-        self.kernel_events = None
 
     def _param_ptrs(self):
         """Device pointers of the live parameters (fp32, contiguous), in _ltr_params() order -- read every step."""
@@ -152,71 +117,38 @@ class LinearFusedRanker(FusedRanker):
     def step(self, X, y, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False, y_base=None, base_cols=None,
              _one_pass=None):
         """FusedRanker.step for the folded network (seed is accepted and unused: nothing here is random).  Risk losses: y_base or
-        base_cols as in FusedRanker.step; `_one_pass=False` sends a Listnet form through the multi-launch chain (tests, benchmarks)."""
-        info = self.info
+        base_cols as in FusedRanker.step; `_one_pass=False` sends a Listnet form through the chain (tests, benchmarks)."""
         self._check_trainable(train, keep1, keep2)
-        require_device(X, y)
-        F = info.F
-        if X.dim() != 3 or X.shape[2] != F or tuple(y.shape[:2]) != tuple(X.shape[:2]):
-            raise ValueError(f"expected X [B,S,{F}] and y [B,S], got {tuple(X.shape)} / {tuple(y.shape)}")
-        B, S = int(X.shape[0]), int(X.shape[1])
-        if S < 1 or S > 2048:
-            raise ValueError(f"slate_length {S} outside the supported range 1..2048")
+        B, S = self._batch_shape(X, y)
         if self.risk is not None:
-            return self._step_risk(X, y, B, S, self._risk_inputs(B, S, y_base, base_cols), world_batch, _one_pass)
+            risk_in = self._risk_inputs(B, S, y_base, base_cols)
+            with torch.cuda.device(self.device):
+                self._step_risk(X, y.detach().reshape(B, S).to(torch.float32).contiguous(), risk_in, world_batch, one_pass=_one_pass)
+            self._bind_grads()
+            return self._loss_out
         if y_base is not None or base_cols is not None:
             raise TypeError(f"y_base / base_cols belong to the risk-sensitive losses, not {self.loss!r}")
-        lambda_mean = self.loss_kind == LOSS_LAMBDA and self.reduction == "mean"
-        if lambda_mean and not defer_norm and world_batch not in (None, B):
-            raise ValueError('lambdaLoss reduction="mean" divides by the GLOBAL kept-pair count, which no rank knows before '
-                             "the all-reduce: under data parallel call step(defer_norm=True) (QueryShardedTrainer does)")
-        if B == 0:
-            self.flat_ext.zero_()
-            if self.loss_kind == LOSS_APPROXNDCG and not world_batch and not defer_norm:
-                self.flat[info.n_params] = float("nan")
+        scale = self._listwise_prelude(B, world_batch, defer_norm, "step")
+        if scale is None:
             self._bind_grads()
             return self._loss_out
-        if self.loss_kind == LOSS_LAMBDA and self.lambda_args[1] < 0:
-            self.flat_ext.zero_()
-            if lambda_mean and not defer_norm:
-                self.flat[info.n_params] = float("nan")
-            self._bind_grads()
-            return self._loss_out
-        gb = int(world_batch) if world_batch else B
-        scale = 1.0 / gb if (self.loss_kind == LOSS_APPROXNDCG and not defer_norm) else 1.0
-        if defer_norm and self.loss_kind == LOSS_APPROXNDCG:
-            self._norm.fill_(float(B))
-        self._calls += 1
         h = lib()
-        L, ln = len(info.sizes), int(info.input_norm)
+        F, ln = self.info.F, int(self.info.input_norm)
         with torch.cuda.device(self.device):
-            x2 = self._docs(X)
             yy = y.detach().reshape(B, S).to(torch.float32).contiguous()
-            if self._slate is None or self._slate.numel() < B:
-                self._slate = torch.empty(B, dtype=torch.float32, device=self.device)
-            count = torch.empty(B, dtype=torch.float32, device=self.device) if self.loss_kind == LOSS_LAMBDA else None
-            ps, ptrs = self._param_ptrs()
-            check(h.ltr_linear_fold(L, F, self._sizes, ln, ptrs, _ptr(self.ws), _ptr(self.weff), _stream()), "ltr_linear_fold")
-            sid, kk, sigma, mu, leps, pad, lb = self.lambda_args
-            if self.kernel_events is not None:
-                self.kernel_events[0].record()
+            r = self._prepare(X)
+            count = self._loss_buffers(B, self.loss_kind == LOSS_LAMBDA)
             if h.ltr_linear_fused_supported(F, S):
-                check(h.ltr_linear_fused_step(self.loss_kind, _ptr(x2), _ptr(yy), B, S, F, _ptr(self.weff), ln, self.alpha, self.eps,
-                                              self.pad, int(self.apply_sigmoid), sid, kk, sigma, mu, leps, lb, scale, _ptr(self._slate),
-                                              _ptr(count), _ptr(self.partials), self.grid, _stream()), "ltr_linear_fused_step")
+                sid, kk, sigma, mu, leps, pad, lb = self.lambda_args
+
+                def one_launch():
+                    check(h.ltr_linear_fused_step(self.loss_kind, _ptr(r.x2), _ptr(yy), B, S, F, _ptr(self.weff), ln, self.alpha, self.eps,
+                                                  self.pad, int(self.apply_sigmoid), sid, kk, sigma, mu, leps, lb, scale, _ptr(self._slate),
+                                                  _ptr(count), _ptr(self.partials), self.grid, _stream()), "ltr_linear_fused_step")
+                self._folded(r, one_launch)
             else:
-                self._three_launches(h, x2, yy, B, S, scale, count)
-            if self.kernel_events is not None:
-                self.kernel_events[1].record()
-            check(h.ltr_linear_unfold_grads(L, F, self._sizes, ln, ptrs, _ptr(self.partials), self.grid, _ptr(self.ws),
-                                            _ptr(self.flat_grad), _stream()), "ltr_linear_unfold_grads")
-            del ps
-            check(h.ltr_reduce_sum_f32(_ptr(self._slate), B, scale, self.flat.data_ptr() + 4 * info.n_params, _stream()),
-                  "ltr_reduce_sum_f32")
-            if lambda_mean:
-                torch.sum(count, dim=0, keepdim=True, out=self._norm)
-                if not defer_norm:
-                    self._divide_by_norm()
+                self._chain(r, self._dense_loss(yy, scale, count))
+            self._listwise_epilogue(B, scale, count, defer_norm)
         self._bind_grads()
         return self._loss_out
 
@@ -229,95 +161,77 @@ class LinearFusedRanker(FusedRanker):
             x2 = x2.contiguous() if not x2.is_contiguous() else x2.clone()
         return x2
 
-    def _step_risk(self, X, y, B, S, risk_in, world_batch, one_pass=None):
-        """The risk step of the folded network (module docstring): one pass over X for the Listnet forms where the one-launch tile kernel
-        takes (F, S), the multi-launch chain otherwise.  The gather, the tail and the loss slot are risk_step's, as for DoubleLayerNet."""
-        from . import risk_step as RS
-        info, R = self.info, self.risk
-        F, L, ln = info.F, len(info.sizes), int(info.input_norm)
-        yb, cache, n_c = risk_in
-        nsys = 1 + n_c
-        n = B * S
-        h = lib()
+    def _prepare(self, X, keep1=None, keep2=None, seed=None, train=None):
+        """FusedRanker._prepare for the folded network: X as [n_docs, F] rows and the live parameters' pointers (nothing here is random;
+        `_calls` counts the executed steps)."""
         self._calls += 1
+        x2 = self._docs(X)
+        ps, ptrs = self._param_ptrs()
+        return SimpleNamespace(x2=x2, n=int(x2.shape[0]), ps=ps, ptrs=ptrs)
+
+    def _folded(self, rows, launches):
+        """ltr_linear_fold (w_eff, b_eff from the live parameters) -> launches(), which leave [Ghat | G_1] partials in `partials` ->
+        ltr_linear_unfold_grads into `flat_grad`.  `kernel_events` bracket everything between the two."""
+        h, info = lib(), self.info
+        F, L, ln = info.F, len(info.sizes), int(info.input_norm)
+        check(h.ltr_linear_fold(L, F, self._sizes, ln, rows.ptrs, _ptr(self.ws), _ptr(self.weff), _stream()), "ltr_linear_fold")
+        if self.kernel_events is not None:
+            self.kernel_events[0].record()
+        launches()
+        if self.kernel_events is not None:
+            self.kernel_events[1].record()
+        check(h.ltr_linear_unfold_grads(L, F, self._sizes, ln, rows.ptrs, _ptr(self.partials), self.grid, _ptr(self.ws),
+                                        _ptr(self.flat_grad), _stream()), "ltr_linear_unfold_grads")
+
+    def _chain(self, rows, loss_launches):
+        """Any slate length, every loss: fold -> scores (GEMV, LayerNorm statistics) -> loss_launches(scores, ds), which fill
+        d loss / d scores -> gradient partials (X re-read, weighted by d loss / d s) -> unfold."""
+        h, n = lib(), rows.n
+        F, ln = self.info.F, int(self.info.input_norm)
+
+        def launches():
+            if self._bufs is None or self._bufs[0].numel() < n:
+                self._bufs = [torch.empty(n, dtype=torch.float32, device=self.device),
+                              torch.empty(n, dtype=torch.float32, device=self.device),
+                              torch.empty(2 * n, dtype=torch.float32, device=self.device)]
+            scores, ds, stats = self._bufs
+            check(h.ltr_linear_scores(_ptr(rows.x2), n, F, _ptr(self.weff), ln, _ptr(scores), _ptr(stats), _stream()), "ltr_linear_scores")
+            loss_launches(scores, ds)
+            check(h.ltr_linear_grad_partials(_ptr(rows.x2), n, F, _ptr(ds), _ptr(stats), ln, _ptr(self.partials), self.grid, _stream()),
+                  "ltr_linear_grad_partials")
+        self._folded(rows, launches)
+
+    def _step_risk(self, X, yy, risk_in, world_batch, keep1=None, keep2=None, seed=None, train=None, one_pass=None):
+        """The risk step of the folded network (module docstring): one pass over X for the Listnet forms where the one-launch tile kernel
+        takes (F, S), FusedRanker._step_risk's chain otherwise.  The gather, the tail and the loss slot are risk_step's either way."""
+        from . import risk_step as RS
+        h, R = lib(), self.risk
+        F, ln = self.info.F, int(self.info.input_norm)
+        B, S = yy.shape
+        yb, cache, n_c = risk_in
         fused_ok = (not R.lam) and bool(h.ltr_linear_fused_supported(F, S))
         if one_pass and not fused_ok:
             raise NotImplementedError(f"{R.name}: the one-pass kernel takes the Listnet forms at S in (32, 64, 128), F % 4 == 0, F <= 256")
         one_pass = fused_ok if one_pass is None else bool(one_pass)
-        with torch.cuda.device(self.device):
-            x2 = self._docs(X)
-            yy = y.detach().reshape(B, S).to(torch.float32).contiguous()
-            if cache is None and not R.lam and B > 0:
-                # Listnet forms: the baselines' columns are O(S) work per system, so y_base= is base_cols= of this batch and one code
-                # path feeds both kernels.  (The Lambda forms' constant columns are S^2 pair sweeps, n_base + 1 of them: with y_base
-                # they run once inside risk_step.matrix's uncached launch, whose matrix is bitwise the cached one.)
-                cache, yb = RS.baseline_columns(R, yy, yb), None
-            dp = (self.risk_group, self.risk_rank, self.risk_world)
-            mat, send, bmax = RS.matrix_rows(R, self.device, dp, B, nsys, world_batch)
-            ps, ptrs = self._param_ptrs()
-            if B > 0:
-                check(h.ltr_linear_fold(L, F, self._sizes, ln, ptrs, _ptr(self.ws), _ptr(self.weff), _stream()), "ltr_linear_fold")
-                if self.kernel_events is not None:
-                    self.kernel_events[0].record()
-                if one_pass:
-                    if self._rows is None or self._rows.numel() < B * (F + 1):
-                        self._rows = torch.empty(B * (F + 1), dtype=torch.float32, device=self.device)
-                    cs_ = int(cache.stride(0)) if B > 1 else int(cache.shape[1])
-                    check(h.ltr_linear_risk_rows(_ptr(x2), _ptr(yy), B, S, F, _ptr(self.weff), ln, R.mode, R.lt, _ptr(cache), cs_, n_c,
-                                                 _ptr(mat), nsys, _ptr(self._rows), self.grid, _stream()), "ltr_linear_risk_rows")
-                else:
-                    if self._bufs is None or self._bufs[0].numel() < n:
-                        self._bufs = [torch.empty(n, dtype=torch.float32, device=self.device),
-                                      torch.empty(n, dtype=torch.float32, device=self.device),
-                                      torch.empty(2 * n, dtype=torch.float32, device=self.device)]
-                    if self._jac is None or self._jac.numel() < n:
-                        self._jac = torch.empty(n, dtype=torch.float32, device=self.device)
-                    scores, ds, stats = self._bufs
-                    jac = self._jac
-                    check(h.ltr_linear_scores(_ptr(x2), n, F, _ptr(self.weff), ln, _ptr(scores), _ptr(stats), _stream()),
-                          "ltr_linear_scores")
-                    RS.matrix(h, R, scores[:n].view(B, S), yy, yb, cache, n_c, mat, jac)
-            coef, _dmat = RS.run_tail(h, R, dp, self.flat[info.n_params:info.n_params + 1], mat, send, bmax, B, nsys)
-            if B == 0:
-                self.flat_grad.zero_()
-                self._bind_grads()
-                return self._loss_out
-            if one_pass:
-                check(h.ltr_linear_risk_combine(_ptr(self._rows), coef, nsys, B, F, _ptr(self.partials), self.grid, _stream()),
-                      "ltr_linear_risk_combine")
-            else:
-                RS.scores_grad(h, R, scores, yy, jac, coef, nsys, ds)
-                check(h.ltr_linear_grad_partials(_ptr(x2), n, F, _ptr(ds), _ptr(stats), ln, _ptr(self.partials), self.grid, _stream()),
-                      "ltr_linear_grad_partials")
-            if self.kernel_events is not None:
-                self.kernel_events[1].record()
-            check(h.ltr_linear_unfold_grads(L, F, self._sizes, ln, ptrs, _ptr(self.partials), self.grid, _ptr(self.ws),
-                                            _ptr(self.flat_grad), _stream()), "ltr_linear_unfold_grads")
-            del ps
-        self._bind_grads()
-        return self._loss_out
+        if cache is None and not R.lam and B > 0:
+            # Listnet forms: the baselines' columns are O(S) work per system, so y_base= is base_cols= of this batch and one code
+            # path feeds both kernels.  (The Lambda forms' constant columns are S^2 pair sweeps, n_base + 1 of them: with y_base
+            # they run once inside risk_step.matrix's uncached launch, whose matrix is bitwise the cached one.)
+            cache, yb = RS.baseline_columns(R, yy, yb), None
+        if not one_pass or B == 0:
+            return super()._step_risk(X, yy, (yb, cache, n_c), world_batch)
+        nsys = 1 + n_c
+        dp = (self.risk_group, self.risk_rank, self.risk_world)
+        rows = self._prepare(X)
+        mat, send, bmax = RS.matrix_rows(R, self.device, dp, B, nsys, world_batch)
+        if self._rows is None or self._rows.numel() < B * (F + 1):
+            self._rows = torch.empty(B * (F + 1), dtype=torch.float32, device=self.device)
 
-    def _three_launches(self, h, x2, yy, B, S, scale, count):
-        """Any slate length: scores (GEMV, LayerNorm statistics) -> the standalone loss kernel -> gradient partials (X re-read,
-        weighted by d loss / d s)."""
-        n = B * S
-        F, ln = self.info.F, int(self.info.input_norm)
-        if self._bufs is None or self._bufs[0].numel() < n:
-            self._bufs = [torch.empty(n, dtype=torch.float32, device=self.device),
-                          torch.empty(n, dtype=torch.float32, device=self.device),
-                          torch.empty(2 * n, dtype=torch.float32, device=self.device)]
-        scores, ds, stats = self._bufs
-        check(h.ltr_linear_scores(_ptr(x2), n, F, _ptr(self.weff), ln, _ptr(scores), _ptr(stats), _stream()), "ltr_linear_scores")
-        if self.loss_kind == LOSS_APPROXNDCG:
-            check(h.ltr_approxndcg_fwd_bwd(_ptr(scores), _ptr(yy), B, S, self.alpha, self.eps, self.pad, scale, _ptr(self._slate),
-                                           _ptr(ds), _stream()), "ltr_approxndcg_fwd_bwd")
-        elif self.loss_kind == LOSS_LISTNET:
-            check(h.ltr_listnet_fwd_bwd(_ptr(yy), _ptr(scores), B, S, int(self.apply_sigmoid), scale, _ptr(self._slate), _ptr(ds),
-                                        _stream()), "ltr_listnet_fwd_bwd")
-        else:
-            sid, kk, sigma, mu, eps, pad, lb = self.lambda_args
-            check(h.ltr_lambda_fwd_bwd(_ptr(scores), _ptr(yy), B, S, sid, kk, sigma, mu, eps, pad, lb, scale, _ptr(self._slate),
-                                       _ptr(count), _ptr(ds), _stream()), "ltr_lambda_fwd_bwd")
-        check(h.ltr_linear_grad_partials(_ptr(x2), n, F, _ptr(ds), _ptr(stats), ln, _ptr(self.partials), self.grid, _stream()),
-              "ltr_linear_grad_partials")
-
+        def one_pass_launches():
+            cs_ = int(cache.stride(0)) if B > 1 else int(cache.shape[1])
+            check(h.ltr_linear_risk_rows(_ptr(rows.x2), _ptr(yy), B, S, F, _ptr(self.weff), ln, R.mode, R.lt, _ptr(cache), cs_, n_c,
+                                         _ptr(mat), nsys, _ptr(self._rows), self.grid, _stream()), "ltr_linear_risk_rows")
+            coef, _dmat = RS.run_tail(h, R, dp, self.flat[self.info.n_params:self.info.n_params + 1], mat, send, bmax, B, nsys)
+            check(h.ltr_linear_risk_combine(_ptr(self._rows), coef, nsys, B, F, _ptr(self.partials), self.grid, _stream()),
+                  "ltr_linear_risk_combine")
+        self._folded(rows, one_pass_launches)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .functional import MAX_SLATE, SCHEME_IDS, _f32, _lambda_args, _ptr, _reduce, _stream, require_device   # noqa: F401
+from .functional import MAX_SLATE, _f32, _lambda_args, _ptr, _reduce, _stream, require_device
 
 # Upper ends of the length tiers.  Powers of two (the geometry rule above), with 256 on its own: lambdaLoss sends 256 .. 1024
 # down the rank-space kernel (every scheme but ndcgLoss1), 129 .. 255 down the document-order one.
@@ -303,143 +303,48 @@ def ndcg_of_lists(true_lists, pred_lists, **kw):
 
 
 # ------------------------------------------------------------------------------------------------------- training step
+def _step_batch(self, X, y, slates, train, keep1, keep2):
+    """The host checks every ragged training step starts with -> (slates on X's device, y as [n_docs])."""
+    self._check_trainable(train, keep1, keep2)
+    require_device(X, y)
+    slates = _slates_on(slates, X.device)
+    n, F = slates.n_docs, self.info.F
+    if X.dim() != 2 or X.shape[1] != F or int(X.shape[0]) != n:
+        raise ValueError(f"expected X [n_docs = {n}, {F}], got {tuple(X.shape)}")
+    return slates, _flat(y, "y", n)
+
+
 def step_ragged(ranker, X, y, slates, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False, y_base=None,
                 base_cols=None):
-    """FusedRanker.step_ragged: the three-launch chain (scorer forward with saved activations -> loss -> scorer backward; for the
+    """FusedRanker.step_ragged: the ranker's chain (scorer forward with saved activations -> loss -> scorer backward; for the
     folded make_model ranker scores -> loss -> gradient partials) with the ragged loss launches in the middle.  Same flat
     [grads | loss | normaliser] buffer, same deferred-normalisation protocol as `step` (normaliser: the query count for approxNDCG,
     the kept-pair count for lambdaLoss "mean").  The six risk-sensitive losses: _step_ragged_risk below."""
-    from .scorer import LOSS_APPROXNDCG, LOSS_LAMBDA
+    from .scorer import LOSS_LAMBDA
     self = ranker
     if self.risk is not None:
         return _step_ragged_risk(self, X, y, slates, world_batch, keep1, keep2, seed, train, y_base, base_cols)
     if y_base is not None or base_cols is not None:
         raise TypeError(f"y_base / base_cols belong to the risk-sensitive losses, not {self.loss!r}")
-    linear = not hasattr(self, "packed")
-    if linear:
-        self._check_trainable(train, keep1, keep2)
-    info = self.info
-    require_device(X, y)
-    slates = _slates_on(slates, X.device)
-    n, Q = slates.n_docs, slates.n_queries
-    if X.dim() != 2 or X.shape[1] != info.F or int(X.shape[0]) != n:
-        raise ValueError(f"expected X [n_docs = {n}, {info.F}], got {tuple(X.shape)}")
-    y1 = _flat(y, "y", n)
-    n_par = info.n_params
-    lambda_mean = self.loss_kind == LOSS_LAMBDA and self.reduction == "mean"
-    if lambda_mean and not defer_norm and world_batch not in (None, Q):
-        raise ValueError('lambdaLoss reduction="mean" divides by the GLOBAL kept-pair count, which no rank knows before '
-                         "the all-reduce: under data parallel call step_ragged(defer_norm=True)")
-    if Q == 0:
-        self.flat_ext.zero_()
-        if self.loss_kind == LOSS_APPROXNDCG and not world_batch and not defer_norm:
-            self.flat[n_par] = float("nan")
+    slates, y1 = _step_batch(self, X, y, slates, train, keep1, keep2)
+    Q = slates.n_queries
+    scale = self._listwise_prelude(Q, world_batch, defer_norm, "step_ragged")
+    if scale is None:
         self._bind_grads()
         return self._loss_out
-    if self.loss_kind == LOSS_LAMBDA and self.lambda_args[1] < 0:      # k = 0 keeps no pair
-        self.flat_ext.zero_()
-        if lambda_mean and not defer_norm:
-            self.flat[n_par] = float("nan")
-        self._bind_grads()
-        return self._loss_out
-    gb = int(world_batch) if world_batch else Q
-    scale = 1.0 / gb if (self.loss_kind == LOSS_APPROXNDCG and not defer_norm) else 1.0
-    if defer_norm and self.loss_kind == LOSS_APPROXNDCG:
-        self._norm.fill_(float(Q))
     h = lib()
-    if self.loss_kind == LOSS_APPROXNDCG:
-        largs = (self.alpha, self.eps, self.pad)
-    elif self.loss_kind == LOSS_LAMBDA:
-        largs = self.lambda_args
-    else:
-        largs = self.apply_sigmoid
     with torch.cuda.device(self.device):
         yy = y1.detach().to(torch.float32).contiguous()
-        if self._slate is None or self._slate.numel() < Q:
-            self._slate = torch.empty(Q, dtype=torch.float32, device=self.device)
-        count = torch.empty(Q, dtype=torch.float32, device=self.device) if self.loss_kind == LOSS_LAMBDA else None
+        count = self._loss_buffers(Q, self.loss_kind == LOSS_LAMBDA)
 
         def loss_launches(scores, ds):
-            launch_loss(h, self.loss_kind, slates, _ptr(scores), _ptr(yy), _ptr(self._slate), _ptr(count), _ptr(ds), scale, largs)
+            launch_loss(h, self.loss_kind, slates, _ptr(scores), _ptr(yy), _ptr(self._slate), _ptr(count), _ptr(ds), scale,
+                        self._loss_args())
 
-        if linear:
-            _linear_chain(self, h, X, n, loss_launches)
-        else:
-            _mlp_chain(self, h, X, n, keep1, keep2, seed, train, loss_launches)
-        check(h.ltr_reduce_sum_f32(_ptr(self._slate), Q, scale, self.flat.data_ptr() + 4 * n_par, _stream()), "ltr_reduce_sum_f32")
-        if lambda_mean:
-            torch.sum(count, dim=0, keepdim=True, out=self._norm)
-            if not defer_norm:
-                self._divide_by_norm()
+        self._chain(self._prepare(X, keep1, keep2, seed, train), loss_launches)
+        self._listwise_epilogue(Q, scale, count, defer_norm)
     self._bind_grads()
     return self._loss_out
-
-
-def _mlp_chain(self, h, X, n, keep1, keep2, seed, train, loss_launches):
-    """FusedRanker._step_three_launches on [n_docs, F] rows."""
-    from . import scorer as S
-    info = self.info
-    train = self.module.training if train is None else train
-    dropout = S.drop_code(bool(train and self.module._ltr_dropout), getattr(getattr(self.module, "dropout", None), "p", 0.5))
-    if seed is None:
-        seed = S.next_seed(self._calls) ^ ((self.seed_salt * 0xA24BAED4963EE407) & S._MASK64)
-    seed = int(seed) & S._MASK64
-    self._calls += 1
-    dev = self.device
-    x2 = S._docs(X, info)
-    k1, k2 = S._mask(keep1, n, info.H1, info.cH1), S._mask(keep2, n, info.H2, info.cH2)
-    fold = self.fold32 if (k1 is None and k2 is None) else None
-    net, packed, partials, pf = self.net, self.packed, self.partials, None
-    if fold is None:
-        S.pack_params(info.handle, self.params, out=self.packed)
-    else:
-        pf = S._params_f32(self.params)
-        copies = fold.H1 // 32
-        fw = S.triple_fold(pf, copies, [self.fold_w[0][:fold.H1], self.fold_w[1][:fold.H1], self.fold_w[2][:, :fold.H1]])
-        packed = self.fold_packed[:fold.packed_floats]
-        S.pack_params(fold.handle, fw + [pf[5]], out=packed)
-        net, partials = fold.net, self.fold_partials
-    scores = torch.empty(n, dtype=torch.float32, device=dev)
-    ds = torch.empty(n, dtype=torch.float32, device=dev)
-    n_acts = int(h.ltr_mlp_acts_floats(net, n))
-    if self._acts is None or self._acts.numel() < n_acts:
-        self._acts = torch.empty(n_acts, dtype=torch.float32, device=dev)
-    check(h.ltr_mlp_forward_save(net, _ptr(x2), n, _ptr(packed), int(dropout), seed, _ptr(k1), _ptr(k2), _ptr(scores),
-                                 _ptr(self._acts), self.grid, _stream()), "ltr_mlp_forward_save")
-    loss_launches(scores, ds)
-    if self.kernel_events is not None:
-        self.kernel_events[0].record()
-    check(h.ltr_mlp_backward_saved(net, _ptr(x2), n, _ptr(packed), int(dropout), _ptr(self._acts), _ptr(ds), _ptr(partials),
-                                   self.grid, _stream()), "ltr_mlp_backward_saved")
-    if self.kernel_events is not None:
-        self.kernel_events[1].record()
-    self._reduce(fold, pf, partials, self.grid)
-
-
-def _linear_chain(self, h, X, n, loss_launches):
-    """LinearFusedRanker's fold -> _three_launches -> unfold on [n_docs, F] rows."""
-    info = self.info
-    F, L, ln = info.F, len(info.sizes), int(info.input_norm)
-    self._calls += 1
-    x2 = self._docs(X)
-    ps, ptrs = self._param_ptrs()
-    check(h.ltr_linear_fold(L, F, self._sizes, ln, ptrs, _ptr(self.ws), _ptr(self.weff), _stream()), "ltr_linear_fold")
-    if self.kernel_events is not None:
-        self.kernel_events[0].record()
-    if self._bufs is None or self._bufs[0].numel() < n:
-        self._bufs = [torch.empty(n, dtype=torch.float32, device=self.device),
-                      torch.empty(n, dtype=torch.float32, device=self.device),
-                      torch.empty(2 * n, dtype=torch.float32, device=self.device)]
-    scores, ds, stats = self._bufs
-    check(h.ltr_linear_scores(_ptr(x2), n, F, _ptr(self.weff), ln, _ptr(scores), _ptr(stats), _stream()), "ltr_linear_scores")
-    loss_launches(scores, ds)
-    check(h.ltr_linear_grad_partials(_ptr(x2), n, F, _ptr(ds), _ptr(stats), ln, _ptr(self.partials), self.grid, _stream()),
-          "ltr_linear_grad_partials")
-    if self.kernel_events is not None:
-        self.kernel_events[1].record()
-    check(h.ltr_linear_unfold_grads(L, F, self._sizes, ln, ptrs, _ptr(self.partials), self.grid, _ptr(self.ws), _ptr(self.flat_grad),
-                                    _stream()), "ltr_linear_unfold_grads")
-    del ps
 
 
 # ------------------------------------------------------------------------------------------------------- risk-sensitive losses
@@ -565,20 +470,12 @@ def baseline_columns(spec, slates, yy, yb):
 
 def _step_ragged_risk(self, X, y, slates, world_batch, keep1, keep2, seed, train, y_base, base_cols):
     """FusedRanker.step_ragged for a risk loss: scorer forward with saved activations -> matrix rows + jac -> [all_gather] -> tail ->
-    scores gradient -> scorer backward -> reduce: FusedRanker._step_risk / LinearFusedRanker._step_risk's chain on [n_docs, F] rows."""
+    scores gradient -> scorer backward -> reduce: FusedRanker._step_risk on [n_docs, F] rows, through the ranker's own chain."""
     from . import risk_step as RS
     R = self.risk
     check_risk_batch(R, slates, y_base, base_cols, 2 if self.risk_world <= 1 else 0)
-    linear = not hasattr(self, "packed")
-    if linear:
-        self._check_trainable(train, keep1, keep2)
-    info = self.info
-    require_device(X, y)
-    slates = _slates_on(slates, X.device)
+    slates, y1 = _step_batch(self, X, y, slates, train, keep1, keep2)
     n, Q = slates.n_docs, slates.n_queries
-    if X.dim() != 2 or X.shape[1] != info.F or int(X.shape[0]) != n:
-        raise ValueError(f"expected X [n_docs = {n}, {info.F}], got {tuple(X.shape)}")
-    y1 = _flat(y, "y", n)
     yb = cache = None
     if base_cols is not None:
         require_device(*[t for t in base_cols if torch.is_tensor(t)])
@@ -589,7 +486,7 @@ def _step_ragged_risk(self, X, y, slates, world_batch, keep1, keep2, seed, train
         yb = risk_baselines(R, n, y_base)
         nsys = 1 + R.n_const(int(yb.shape[1]))
     h = lib()
-    n_par = info.n_params
+    n_par = self.info.n_params
     dp = (self.risk_group, self.risk_rank, self.risk_world)
     with torch.cuda.device(self.device):
         yy = y1.detach().to(torch.float32).contiguous()
@@ -605,10 +502,8 @@ def _step_ragged_risk(self, X, y, slates, world_batch, keep1, keep2, seed, train
         if Q == 0:                                   # a rank without queries still joins the gather and runs the tail
             RS.run_tail(h, R, dp, slot, mat, send, bmax, Q, nsys)
             self.flat_grad.zero_()
-        elif linear:
-            _linear_chain(self, h, X, n, loss_launches)
         else:
-            _mlp_chain(self, h, X, n, keep1, keep2, seed, train, loss_launches)
+            self._chain(self._prepare(X, keep1, keep2, seed, train), loss_launches)
     self._bind_grads()
     return self._loss_out
 

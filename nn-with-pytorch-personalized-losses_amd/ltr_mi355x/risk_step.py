@@ -22,11 +22,10 @@ its own rows.  The trainer's one all-reduce of [grads | loss] then sums the weig
 import torch
 
 from ._lib import check
-from .functional import _lambda_args, _ptr, _stream
+from .functional import MAX_SLATE, _lambda_args, _ptr, _stream   # noqa: F401  (MAX_SLATE: read as risk_step.MAX_SLATE)
 
 RISK_LOSSES = ("geoRiskListnetLoss", "geoRiskLambdaLoss", "zRiskListnetLoss", "zRiskLambdaLoss", "tRiskListnetLoss", "tRiskLambdaLoss")
 RISK_Z, RISK_GEO = 0, 1
-MAX_SLATE = 2048
 _GZ = dict(alpha=5, listnet_transformation=1, return_strategy=1, negative=1, add_ideal_ranking_to_mat=1)
 _T = dict(alpha=5, listnet_transformation=1, negative=1)
 # the reference signatures' keyword arguments and defaults (riskLosses.py:8, :63, :128, :183, :247, :294)

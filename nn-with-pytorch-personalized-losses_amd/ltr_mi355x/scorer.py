@@ -9,6 +9,7 @@ Two ways in, same kernels:
     (the buffer the data-parallel all-reduce runs on).
 """
 import ctypes
+from types import SimpleNamespace
 
 import torch
 
@@ -303,6 +304,20 @@ def _dropout_keep_mask_half(seed, layer, n_docs, H, device):
     return out
 
 
+def launch_loss(h, kind, B, S, scores, labels, slate_loss, count, ds, scale, args):
+    """ragged.launch_loss for a rectangular batch [B, S]: one launch.  kind LOSS_APPROXNDCG (args = alpha, eps, pad), LOSS_LISTNET
+    (args = apply_sigmoid; `labels` are y_true), LOSS_LAMBDA (args = _lambda_args).  Pointers are raw device addresses (None = NULL)."""
+    if kind == LOSS_APPROXNDCG:
+        alpha, eps, pad = args
+        check(h.ltr_approxndcg_fwd_bwd(scores, labels, B, S, alpha, eps, pad, scale, slate_loss, ds, _stream()), "ltr_approxndcg_fwd_bwd")
+    elif kind == LOSS_LISTNET:
+        check(h.ltr_listnet_fwd_bwd(labels, scores, B, S, int(args), scale, slate_loss, ds, _stream()), "ltr_listnet_fwd_bwd")
+    else:
+        sid, kk, sigma, mu, eps, pad, lb = args
+        check(h.ltr_lambda_fwd_bwd(scores, labels, B, S, sid, kk, sigma, mu, eps, pad, lb, scale, slate_loss, count, ds, _stream()),
+              "ltr_lambda_fwd_bwd")
+
+
 class FusedRanker:
     """One-launch training pass for a DoubleLayerNet / TripleLayerNet -- or an FC-only make_model LTRModel, which runs folded
     (ltr_mi355x.linear.LinearFusedRanker) -- with a listwise loss.
@@ -335,57 +350,23 @@ class FusedRanker:
     def __init__(self, module, loss="approxNDCG", alpha=1.0, eps=1e-10, padded_value_indicator=-1,
                  apply_sigmoid=False, grid=None, weighing_scheme=None, k=None, sigma=1.0, mu=10.0,
                  reduction="sum", reduction_log="binary", risk_args=None):
-        if loss not in self.LOSSES:
-            raise KeyError(f"fused loss must be one of {sorted(self.LOSSES)}, got {loss!r}")
-        self.risk = None
-        if self.LOSSES[loss] == LOSS_RISK:
-            from .risk_step import RiskSpec
-            self.risk = RiskSpec(loss, risk_args)
-            # data parallel: ltr_mi355x.dp.QueryShardedTrainer sets (group, rank, world) -- the risk step all-gathers its matrix rows
-            self.risk_group = None
-            self.risk_rank, self.risk_world = 0, 1
-        elif risk_args is not None:
-            raise TypeError(f"risk_args belongs to the risk-sensitive losses, not {loss!r}")
+        self._init_risk(loss, risk_args)
         self.module = module
         if module._ltr_net == NET_WIDE:
             raise NotImplementedError("the fused step is built for scorers of up to 136 input features; wider networks run as "
                                       "net(x, None, None) + the loss + backward() (ltr_mi355x.scorer.wide_forward)")
         self.info = NetInfo.get(module._ltr_net)
         self.net = self.info.net           # the compiled network id the kernels run
-        self.loss = loss
-        self.loss_kind = self.LOSSES[loss]
-        self.alpha, self.eps, self.pad = float(alpha), float(eps), float(padded_value_indicator)
-        self.apply_sigmoid = bool(apply_sigmoid)
-        if self.loss_kind == LOSS_LAMBDA:
-            from .functional import _lambda_args
-            if reduction not in ("sum", "mean"):
-                raise ValueError("Reduction method can be either sum or mean")
-            self.lambda_args = _lambda_args(eps, padded_value_indicator, weighing_scheme, k, sigma, mu, reduction_log)
-        self.reduction = reduction
+        self._init_loss(loss, alpha, eps, padded_value_indicator, apply_sigmoid, weighing_scheme, k, sigma, mu, reduction, reduction_log)
         self.params = module._ltr_params()
         require_device(*self.params)
-        dev = self.params[0].device
-        self.device = dev
+        dev = self.device = self.params[0].device
         self.grid = int(grid) if grid else int(lib().ltr_fused_grid(self.net, cu_count(dev)))     # persistent workgroups (1 or 2 per CU)
-        # one flat fp32 buffer [all parameter gradients | loss | normaliser]: the ONLY thing data parallel all-reduces.
-        # `flat` = [grads | loss] (what the optimizer and callers read); `flat_ext` adds the normaliser slot of the
-        # deferred-normalisation protocol (step(defer_norm=True) -> all-reduce(flat_ext) -> finish_norm()): the local
-        # batch size for the batch-mean loss (approxNDCG.py:53), the local kept-pair count for lambdaLoss
-        # reduction="mean" (lambdaL.py:88-89) -- so the GLOBAL mean needs neither a second collective nor a host sync.
-        self.flat_ext = torch.zeros(self.info.n_params + 2, dtype=torch.float32, device=dev)
-        self.flat = self.flat_ext[:self.info.n_params + 1]
-        self.flat_grad = self.flat[:self.info.n_params]
-        self._norm = self.flat_ext[self.info.n_params + 1:]          # 1-element view
-        self._grad_views = []
-        off = 0
-        for p in self.params:           # every p.grad is a view into the flat buffer
-            self._grad_views.append(self.flat_grad[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        self._bind_grads()
+        self._init_flat()
         self.packed = torch.empty(self.info.packed_floats, dtype=torch.float32, device=dev)
         self.partials = torch.empty(self.grid * self.info.partial_floats, dtype=torch.float32, device=dev)
         # TripleLayerNet on the 136-feature collection runs FOLDED (triple_folds above): the one-launch step on the two-layer
-        # kernel with two document-split copies of the 32 units (NET_TRIPLE_FOLDED), the three-launch path on the plain
+        # kernel with two document-split copies of the 32 units (NET_TRIPLE_FOLDED), the chain on the plain
         # 136 -> 32 -> 1 network (NET_TRIPLE_FOLDED_32)
         self.fold = self.fold32 = None
         if triple_folds(self.info.handle):
@@ -398,9 +379,56 @@ class FusedRanker:
             self.fold_partials = torch.empty(max(self.fold_grid * fi.partial_floats, self.grid * fi32.partial_floats), dtype=torch.float32,
                                              device=dev)
             self.fold_flat = torch.empty(fi.n_params, dtype=torch.float32, device=dev)
-        self._loss_out = self.flat[self.info.n_params]
-        self._slate = None
-        self._acts = None              # saved hidden activations of the three-launch path (grown on demand)
+        self._acts = None              # saved hidden activations of the chain (grown on demand)
+
+    # ------------------------------------------------------------------------- constructor parts both ranker classes run
+    def _init_risk(self, loss, risk_args):
+        """The loss name and the options of a risk loss: their errors come first, they need no device."""
+        if loss not in self.LOSSES:
+            raise KeyError(f"fused loss must be one of {sorted(self.LOSSES)}, got {loss!r}")
+        self.risk = None
+        if self.LOSSES[loss] == LOSS_RISK:
+            from .risk_step import RiskSpec
+            self.risk = RiskSpec(loss, risk_args)
+            # data parallel: ltr_mi355x.dp.QueryShardedTrainer sets (group, rank, world) -- the risk step all-gathers its matrix rows
+            self.risk_group = None
+            self.risk_rank, self.risk_world = 0, 1
+        elif risk_args is not None:
+            raise TypeError(f"risk_args belongs to the risk-sensitive losses, not {loss!r}")
+
+    def _init_loss(self, loss, alpha, eps, padded_value_indicator, apply_sigmoid, weighing_scheme, k, sigma, mu, reduction, reduction_log):
+        """The options of the three listwise losses."""
+        self.loss = loss
+        self.loss_kind = self.LOSSES[loss]
+        self.alpha, self.eps, self.pad = float(alpha), float(eps), float(padded_value_indicator)
+        self.apply_sigmoid = bool(apply_sigmoid)
+        self.lambda_args = (4, 0, 1.0, 10.0, 1e-10, -1.0, 0)       # what a launcher that takes every loss's arguments gets for the other two
+        if self.loss_kind == LOSS_LAMBDA:
+            from .functional import _lambda_args
+            if reduction not in ("sum", "mean"):
+                raise ValueError("Reduction method can be either sum or mean")
+            self.lambda_args = _lambda_args(eps, padded_value_indicator, weighing_scheme, k, sigma, mu, reduction_log)
+        self.reduction = reduction
+
+    def _init_flat(self):
+        """One flat fp32 buffer [all parameter gradients | loss | normaliser]: the ONLY thing data parallel all-reduces.
+        `flat` = [grads | loss] (what the optimizer and callers read); `flat_ext` adds the normaliser slot of the
+        deferred-normalisation protocol (step(defer_norm=True) -> all-reduce(flat_ext) -> finish_norm()): the local
+        batch size for the batch-mean loss (approxNDCG.py:53), the local kept-pair count for lambdaLoss
+        reduction="mean" (lambdaL.py:88-89) -- so the GLOBAL mean needs neither a second collective nor a host sync."""
+        n_par = self.info.n_params
+        self.flat_ext = torch.zeros(n_par + 2, dtype=torch.float32, device=self.device)
+        self.flat = self.flat_ext[:n_par + 1]
+        self.flat_grad = self.flat[:n_par]
+        self._norm = self.flat_ext[n_par + 1:]          # 1-element view
+        self._grad_views = []
+        off = 0
+        for p in self.params:           # every p.grad is a view into the flat buffer
+            self._grad_views.append(self.flat_grad[off:off + p.numel()].view_as(p))
+            off += p.numel()
+        self._bind_grads()
+        self._loss_out = self.flat[n_par]
+        self._slate = None             # per-query losses of the listwise steps (grown on demand)
         self._calls = 0
         self.seed_salt = 0             # per-rank salt of the dropout stream (data parallel)
         self.kernel_events = None      # optional (start, end) torch.cuda.Event pair bracketing the pipeline kernel
@@ -443,6 +471,147 @@ class FusedRanker:
         self.flat_grad.div_(torch.where(n > 0, n, torch.ones_like(n)))
         self.flat[self.info.n_params:].div_(n)
 
+    # ------------------------------------------------------------------------- what `step` (both classes) and `step_ragged` share
+    def _check_trainable(self, train, keep1, keep2):
+        """Refuse what the scorer cannot train with (LinearFusedRanker: dropout in any form).  These networks take all of it."""
+
+    def _batch_shape(self, X, y):
+        """(B, S) of a rectangular batch, shapes checked."""
+        F = self.info.F
+        require_device(X, y)
+        if X.dim() != 3 or X.shape[2] != F or tuple(y.shape[:2]) != tuple(X.shape[:2]):
+            raise ValueError(f"expected X [B,S,{F}] and y [B,S], got {tuple(X.shape)} / {tuple(y.shape)}")
+        B, S = int(X.shape[0]), int(X.shape[1])
+        if S < 1 or S > 2048:
+            raise ValueError(f"slate_length {S} outside the supported range 1..2048")
+        return B, S
+
+    def _listwise_prelude(self, Q, world_batch, defer_norm, method):
+        """The start of a listwise step on this rank's Q queries.  Returns None where the step is answered here, with `flat_ext` holding
+        the answer (no queries; lambdaLoss k = 0) and `_calls` left alone; otherwise the factor the loss launches and the loss reduce
+        apply, with the normaliser slot set for a deferred approxNDCG."""
+        n_par = self.info.n_params
+        lambda_mean = self.mean_kind == "pairs"
+        if lambda_mean and not defer_norm and world_batch not in (None, Q):
+            raise ValueError('lambdaLoss reduction="mean" divides by the GLOBAL kept-pair count, which no rank knows before '
+                             f"the all-reduce: under data parallel call {method}(defer_norm=True)"
+                             + (" (QueryShardedTrainer does)" if method == "step" else ""))
+        if Q == 0:
+            # no slates on this rank: zero gradient contribution; the loss of an empty batch is what the
+            # reference's reduction gives (mean of nothing = nan, sum of nothing = 0) unless a global batch is set
+            self.flat_ext.zero_()
+            if self.loss_kind == LOSS_APPROXNDCG and not world_batch and not defer_norm:
+                self.flat[n_par] = float("nan")
+            return None
+        if self.loss_kind == LOSS_LAMBDA and self.lambda_args[1] < 0:
+            # k = 0: `ndcg_at_k_mask[:0, :0]` keeps no pair (lambdaL.py:29-30) -> loss 0 ("sum") / nan ("mean" of
+            # nothing), zero gradient, for every slate length
+            self.flat_ext.zero_()
+            if lambda_mean and not defer_norm:
+                self.flat[n_par] = float("nan")
+            return None
+        gb = int(world_batch) if world_batch else Q
+        if defer_norm and self.loss_kind == LOSS_APPROXNDCG:
+            self._norm.fill_(float(Q))
+        # mean over the batch (approxNDCG.py:53) vs sum (listnet.py:16); deferred: sums now, one division after the all-reduce
+        return 1.0 / gb if (self.loss_kind == LOSS_APPROXNDCG and not defer_norm) else 1.0
+
+    def _loss_buffers(self, Q, want_count):
+        """`_slate` grown to Q per-query losses -> the per-query kept-pair counts of lambdaLoss [Q], or None."""
+        if self._slate is None or self._slate.numel() < Q:
+            self._slate = torch.empty(Q, dtype=torch.float32, device=self.device)
+        return torch.empty(Q, dtype=torch.float32, device=self.device) if want_count else None
+
+    def _loss_args(self):
+        """This ranker's `args` of launch_loss / ragged.launch_loss."""
+        if self.loss_kind == LOSS_APPROXNDCG:
+            return self.alpha, self.eps, self.pad
+        return self.lambda_args if self.loss_kind == LOSS_LAMBDA else self.apply_sigmoid
+
+    def _dense_loss(self, yy, scale, count):
+        """The loss launches of a rectangular listwise chain."""
+        B, S = yy.shape
+
+        def loss_launches(scores, ds):
+            launch_loss(lib(), self.loss_kind, B, S, _ptr(scores), _ptr(yy), _ptr(self._slate), _ptr(count), _ptr(ds), scale,
+                        self._loss_args())
+        return loss_launches
+
+    def _listwise_epilogue(self, Q, scale, count, defer_norm):
+        """The end of a listwise step: per-query losses -> the loss slot; lambdaLoss "mean": the kept-pair count -> the normaliser."""
+        check(lib().ltr_reduce_sum_f32(_ptr(self._slate), Q, scale, self.flat.data_ptr() + 4 * self.info.n_params, _stream()),
+              "ltr_reduce_sum_f32")
+        if self.mean_kind == "pairs":
+            # the pair-mean is linear in d loss / d scores: the launches ran in sum form, one division of
+            # [grads | loss] by the kept-pair count follows (here, or after the all-reduce when deferred)
+            torch.sum(count, dim=0, keepdim=True, out=self._norm)
+            if not defer_norm:
+                self._divide_by_norm()
+
+    def _prepare(self, X, keep1, keep2, seed, train, one_launch=False):
+        """What every executed step does before its first scorer launch -> the prepared document rows `_chain` takes: the dropout code
+        and seed (a default seed comes from `_calls`; every call here advances it), X as [n_docs, F] rows, the explicit masks, and the
+        parameters packed for the network the route runs.  Explicit masks: the module's own network.  Otherwise a TripleLayerNet runs
+        folded: the one-launch step `fold` on `fold_grid`, every chain `fold32` on `grid`."""
+        info = self.info
+        train = self.module.training if train is None else train
+        dropout = drop_code(bool(train and self.module._ltr_dropout), getattr(getattr(self.module, "dropout", None), "p", 0.5))
+        if seed is None:
+            seed = next_seed(self._calls) ^ ((self.seed_salt * 0xA24BAED4963EE407) & _MASK64)
+        self._calls += 1
+        x2 = _docs(X, info)
+        n = int(x2.shape[0])
+        k1, k2 = _mask(keep1, n, info.H1, info.cH1), _mask(keep2, n, info.H2, info.cH2)
+        one_launch = one_launch and not (dropout > 1 and k1 is None)      # p != 0.5: only the forward kernels carry that stream
+        fold = (self.fold if one_launch else self.fold32) if (k1 is None and k2 is None) else None
+        net, packed, partials, grid, pf = self.net, self.packed, self.partials, self.grid, None
+        if fold is None:
+            pack_params(info.handle, self.params, out=self.packed)
+        else:
+            pf = _params_f32(self.params)                       # W1, b1, W2, b2, w3, b3
+            copies = fold.H1 // 32
+            fw = triple_fold(pf, copies, [self.fold_w[0][:fold.H1], self.fold_w[1][:fold.H1], self.fold_w[2][:, :fold.H1]])
+            packed = self.fold_packed[:fold.packed_floats]
+            pack_params(fold.handle, fw + [pf[5]], out=packed)
+            net, partials = fold.net, self.fold_partials
+            if one_launch:
+                grid = self.fold_grid
+        return SimpleNamespace(x2=x2, n=n, dropout=int(dropout), seed=int(seed) & _MASK64, k1=k1, k2=k2, one_launch=one_launch, fold=fold,
+                               pf=pf, net=net, packed=packed, partials=partials, grid=grid)
+
+    def _chain(self, rows, loss_launches):
+        """Any slate length, every loss: scorer forward launch (writes the scores AND the post-activation hidden layers, 1 152 B per
+        document for the 136-wide net) -> loss_launches(scores, ds), which fill d loss / d scores -> scorer backward launch that reads
+        h1 / h2 back instead of recomputing fc1 / fc2: ONE forward, like the reference's autograd (main_batch_execution.py:128-170)
+        -> the gradient reduce into `flat_grad`.  The backward kernel is bound by the fp32 matrix pipe; the activation round trip
+        rides on HBM bandwidth it leaves idle."""
+        h, r, dev = lib(), rows, self.device
+        scores = torch.empty(r.n, dtype=torch.float32, device=dev)
+        ds = torch.empty(r.n, dtype=torch.float32, device=dev)
+        n_acts = int(h.ltr_mlp_acts_floats(r.net, r.n))
+        if self._acts is None or self._acts.numel() < n_acts:
+            self._acts = torch.empty(n_acts, dtype=torch.float32, device=dev)
+        check(h.ltr_mlp_forward_save(r.net, _ptr(r.x2), r.n, _ptr(r.packed), r.dropout, r.seed, _ptr(r.k1), _ptr(r.k2),
+                                     _ptr(scores), _ptr(self._acts), self.grid, _stream()), "ltr_mlp_forward_save")
+        loss_launches(scores, ds)
+        if self.kernel_events is not None:
+            self.kernel_events[0].record()
+        check(h.ltr_mlp_backward_saved(r.net, _ptr(r.x2), r.n, _ptr(r.packed), r.dropout, _ptr(self._acts), _ptr(ds),
+                                       _ptr(r.partials), self.grid, _stream()), "ltr_mlp_backward_saved")
+        if self.kernel_events is not None:
+            self.kernel_events[1].record()
+        self._reduce(r.fold, r.pf, r.partials, self.grid)
+
+    def _reduce(self, fold, pf, partials, grid):
+        """Per-workgroup partials -> the flat gradient of the module's own tensors (through the unfold for a folded TripleLayerNet)."""
+        if fold is None:
+            reduce_grads(self.info, partials, grid, self.flat_grad)
+        else:
+            g2 = self.fold_flat[:fold.n_params]
+            reduce_grads(fold, partials, grid, g2)
+            triple_unfold(g2, fold.H1 // 32, pf, self.flat_grad)
+
+    # ------------------------------------------------------------------------------------------ the public steps
     def step(self, X, y, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False, y_base=None, base_cols=None):
         """Run the fused pass on this rank's slates.  Returns the 0-dim LOCAL loss contribution, already
         scaled for the global batch (sum over ranks == the reference's loss on the global batch).
@@ -450,121 +619,59 @@ class FusedRanker:
         all-reduces `flat_ext` and calls `finish_norm()` (ltr_mi355x.dp.QueryShardedTrainer).
         Risk losses: y_base [B, S, n] ([B, S] for tRisk) or base_cols (baseline_columns) -- one of them is required.  Under data
         parallel their loss is the GLOBAL value (on rank 0; 0 elsewhere, so the all-reduced slot holds it once)."""
-        info = self.info
-        require_device(X, y)
-        if X.dim() != 3 or X.shape[2] != info.F or tuple(y.shape[:2]) != tuple(X.shape[:2]):
-            raise ValueError(f"expected X [B,S,{info.F}] and y [B,S], got {tuple(X.shape)} / {tuple(y.shape)}")
-        B, S = int(X.shape[0]), int(X.shape[1])
-        if S < 1 or S > 2048:
-            raise ValueError(f"slate_length {S} outside the supported range 1..2048")
-        risk_in = None
+        B, S = self._batch_shape(X, y)
         if self.risk is not None:
             risk_in = self._risk_inputs(B, S, y_base, base_cols)
-        elif y_base is not None or base_cols is not None:
+            with torch.cuda.device(self.device):
+                self._step_risk(X, y.detach().reshape(B, S).to(torch.float32).contiguous(), risk_in, world_batch, keep1, keep2, seed, train)
+            self._bind_grads()
+            return self._loss_out
+        if y_base is not None or base_cols is not None:
             raise TypeError(f"y_base / base_cols belong to the risk-sensitive losses, not {self.loss!r}")
-        lambda_mean = self.loss_kind == LOSS_LAMBDA and self.reduction == "mean"
-        if lambda_mean and not defer_norm and world_batch not in (None, B):
-            raise ValueError('lambdaLoss reduction="mean" divides by the GLOBAL kept-pair count, which no rank knows before '
-                             "the all-reduce: under data parallel call step(defer_norm=True) (QueryShardedTrainer does)")
-        # one launch when the slate tiles a 128-document super-tile; otherwise forward launch + loss kernel +
-        # backward launch -- same flat gradient buffer either way
-        one_launch = S in (32, 64, 128)       # (and the reference's dropout probability: see below)
-        if B == 0 and self.risk is None:
-            # no slates on this rank: zero gradient contribution; the loss of an empty batch is what the
-            # reference's reduction gives (mean of nothing = nan, sum of nothing = 0) unless a global batch is set
-            self.flat_ext.zero_()
-            if self.loss_kind == LOSS_APPROXNDCG and not world_batch and not defer_norm:
-                self.flat[self.info.n_params] = float("nan")
+        scale = self._listwise_prelude(B, world_batch, defer_norm, "step")
+        if scale is None:
             self._bind_grads()
             return self._loss_out
-        if self.loss_kind == LOSS_LAMBDA and self.lambda_args[1] < 0:
-            # k = 0: `ndcg_at_k_mask[:0, :0]` keeps no pair (lambdaL.py:29-30) -> loss 0 ("sum") / nan ("mean" of
-            # nothing), zero gradient, for every slate length
-            self.flat_ext.zero_()
-            if lambda_mean and not defer_norm:
-                self.flat[self.info.n_params] = float("nan")
-            self._bind_grads()
-            return self._loss_out
-        gb = int(world_batch) if world_batch else B
-        # mean over the batch (approxNDCG.py:53) vs sum (listnet.py:16); deferred: sums now, one division after the all-reduce
-        scale = 1.0 / gb if (self.loss_kind == LOSS_APPROXNDCG and not defer_norm) else 1.0
-        if defer_norm and self.loss_kind == LOSS_APPROXNDCG:
-            self._norm.fill_(float(B))
-        count = None
-        train = self.module.training if train is None else train
-        dropout = drop_code(bool(train and self.module._ltr_dropout), getattr(getattr(self.module, "dropout", None), "p", 0.5))
-        if seed is None:
-            seed = next_seed(self._calls) ^ ((self.seed_salt * 0xA24BAED4963EE407) & _MASK64)
-        self._calls += 1
         with torch.cuda.device(self.device):
-            x2 = _docs(X, info)
             yy = y.detach().reshape(B, S).to(torch.float32).contiguous()
-            k1, k2 = _mask(keep1, B * S, info.H1, info.cH1), _mask(keep2, B * S, info.H2, info.cH2)
-            if self._slate is None or self._slate.numel() < B:
-                self._slate = torch.empty(B, dtype=torch.float32, device=self.device)
-            h = lib()
-            three = not one_launch or (dropout > 1 and k1 is None) or self.risk is not None  # p != 0.5: only the forward kernels carry that stream
-            fold = (self.fold32 if three else self.fold) if (k1 is None and k2 is None) else None
-            net, packed, partials, grid = self.net, self.packed, self.partials, self.grid
-            pf = None
-            if fold is None:
-                pack_params(self.info.handle, self.params, out=self.packed)
+            # one launch when the slate tiles a 128-document super-tile (and the dropout is the reference's p = 0.5); otherwise the
+            # chain -- same flat gradient buffer either way
+            r = self._prepare(X, keep1, keep2, seed, train, one_launch=S in (32, 64, 128))
+            if not r.one_launch:
+                count = self._loss_buffers(B, self.loss_kind == LOSS_LAMBDA)
+                self._chain(r, self._dense_loss(yy, scale, count))
             else:
-                pf = _params_f32(self.params)                       # W1, b1, W2, b2, w3, b3
-                copies = fold.H1 // 32
-                fw = triple_fold(pf, copies, [self.fold_w[0][:fold.H1], self.fold_w[1][:fold.H1], self.fold_w[2][:, :fold.H1]])
-                packed = self.fold_packed[:fold.packed_floats]
-                pack_params(fold.handle, fw + [pf[5]], out=packed)
-                net, partials, grid = fold.net, self.fold_partials, (self.grid if three else self.fold_grid)
-            if self.risk is not None:
-                out = self._step_risk(h, x2, yy, B, S, dropout, int(seed) & _MASK64, k1, k2, risk_in, world_batch, fold, pf, net, packed,
-                                      partials)
-                self._bind_grads()
-                return out
-            if three:
-                out = self._step_three_launches(h, x2, yy, B, S, dropout, int(seed) & _MASK64, k1, k2, scale, lambda_mean,
-                                                defer_norm, fold, pf, net, packed, partials)
-                self._bind_grads()
-                return out
-            if self.kernel_events is not None:
-                self.kernel_events[0].record()
-            if self.loss_kind == LOSS_LAMBDA:
-                sid, kk, sigma, mu, eps, pad, lb = self.lambda_args
-                if lambda_mean:
-                    count = torch.empty(B, dtype=torch.float32, device=self.device)
-                check(h.ltr_fused_step_lambda(net, _ptr(x2), _ptr(yy), B, S, _ptr(packed), int(dropout),
-                                              int(seed) & _MASK64, _ptr(k1), _ptr(k2), sid, kk, sigma, mu, eps, pad,
-                                              lb, 1.0, _ptr(self._slate), _ptr(count), _ptr(partials), grid,
-                                              _stream()), "ltr_fused_step_lambda")
-            else:
-                check(h.ltr_fused_step(net, self.loss_kind, _ptr(x2), _ptr(yy), B, S, _ptr(packed),
-                                       int(dropout), int(seed) & _MASK64, _ptr(k1), _ptr(k2), self.alpha, self.eps,
-                                       self.pad, int(self.apply_sigmoid), scale, _ptr(self._slate), _ptr(partials),
-                                       grid, _stream()), "ltr_fused_step")
-            if self.kernel_events is not None:
-                self.kernel_events[1].record()
-            self._reduce(fold, pf, partials, grid)
-            check(h.ltr_reduce_sum_f32(_ptr(self._slate), B, scale, self.flat.data_ptr() + 4 * self.info.n_params,
-                                       _stream()), "ltr_reduce_sum_f32")
-            if lambda_mean:
-                # the pair-mean is linear in d loss / d scores: the launch ran in sum form, one division of
-                # [grads | loss] by the kept-pair count follows (here, or after the all-reduce when deferred)
-                torch.sum(count, dim=0, keepdim=True, out=self._norm)
-                if not defer_norm:
-                    self._divide_by_norm()
+                h = lib()
+                count = self._loss_buffers(B, self.mean_kind == "pairs")      # the launch takes NULL where nobody reads the counts
+                if self.kernel_events is not None:
+                    self.kernel_events[0].record()
+                if self.loss_kind == LOSS_LAMBDA:
+                    sid, kk, sigma, mu, eps, pad, lb = self.lambda_args
+                    check(h.ltr_fused_step_lambda(r.net, _ptr(r.x2), _ptr(yy), B, S, _ptr(r.packed), r.dropout, r.seed, _ptr(r.k1),
+                                                  _ptr(r.k2), sid, kk, sigma, mu, eps, pad, lb, 1.0, _ptr(self._slate), _ptr(count),
+                                                  _ptr(r.partials), r.grid, _stream()), "ltr_fused_step_lambda")
+                else:
+                    check(h.ltr_fused_step(r.net, self.loss_kind, _ptr(r.x2), _ptr(yy), B, S, _ptr(r.packed), r.dropout, r.seed,
+                                           _ptr(r.k1), _ptr(r.k2), self.alpha, self.eps, self.pad, int(self.apply_sigmoid), scale,
+                                           _ptr(self._slate), _ptr(r.partials), r.grid, _stream()), "ltr_fused_step")
+                if self.kernel_events is not None:
+                    self.kernel_events[1].record()
+                self._reduce(r.fold, r.pf, r.partials, r.grid)
+            self._listwise_epilogue(B, scale, count, defer_norm)
         self._bind_grads()
         return self._loss_out
 
     def step_ragged(self, X, y, slates, world_batch=None, keep1=None, keep2=None, seed=None, train=None, defer_norm=False, y_base=None,
                     base_cols=None):
         """`step` for queries of unequal length, no padding: X [n_docs, F], y [n_docs], slates a ltr_mi355x.ragged.RaggedSlates
-        (query q owns rows offsets[q] .. offsets[q + 1] - 1).  The three-launch chain with one loss launch per occupied length tier;
+        (query q owns rows offsets[q] .. offsets[q + 1] - 1).  The chain with one loss launch per occupied length tier;
         buffers, return value, `world_batch` (here: the global QUERY count) and defer_norm / finish_norm as in `step`.  Explicit
         masks are [n_docs, H].  Risk losses: y_base [n_docs, n] ([n_docs] for tRisk) or base_cols (baseline_columns_ragged) -- one of
         them is required (neither: NotImplementedError); queries of 2..2048 documents, at least 2 of them in one process."""
         from .ragged import step_ragged
         return step_ragged(self, X, y, slates, world_batch, keep1, keep2, seed, train, defer_norm, y_base, base_cols)
 
+    # ------------------------------------------------------------------------------------------ risk-sensitive losses
     def baseline_columns_ragged(self, y, y_base, slates):
         """The constant part of a risk loss's matrix for the queries of `slates`: (entries [Q, C], ideal_colsum [n_docs] or None --
         the ideal ranking's column sums, Lambda forms only), to pass as step_ragged(..., base_cols=(entries, ideal_colsum)).  Computed
@@ -582,60 +689,6 @@ class FusedRanker:
             yy = ragged._flat(y, "y", n).detach().to(torch.float32).contiguous()
             return ragged.baseline_columns(self.risk, slates, yy, ragged.risk_baselines(self.risk, n, y_base))
 
-    def _reduce(self, fold, pf, partials, grid):
-        """Per-workgroup partials -> the flat gradient of the module's own tensors (through the unfold for a folded TripleLayerNet)."""
-        if fold is None:
-            reduce_grads(self.info, partials, grid, self.flat_grad)
-        else:
-            g2 = self.fold_flat[:fold.n_params]
-            reduce_grads(fold, partials, grid, g2)
-            triple_unfold(g2, fold.H1 // 32, pf, self.flat_grad)
-
-    def _step_three_launches(self, h, x2, yy, B, S, dropout, seed, k1, k2, scale, lambda_mean, defer_norm=False, fold=None, pf=None,
-                             net=None, packed=None, partials=None):
-        """Any slate length (and lambdaLoss "mean"): scorer forward launch (writes the scores AND the post-activation
-        hidden layers, 1 152 B per document for the 136-wide net) -> loss kernel (forward + dL/dscores) -> scorer backward
-        launch that reads h1 / h2 back instead of recomputing fc1 / fc2: ONE forward, like the reference's autograd
-        (main_batch_execution.py:128-170).  The backward kernel is bound by the fp32 matrix pipe; the activation round trip
-        rides on HBM bandwidth it leaves idle."""
-        n = B * S
-        dev = self.device
-        if net is None:
-            net, packed, partials = self.net, self.packed, self.partials
-        scores = torch.empty(n, dtype=torch.float32, device=dev)
-        ds = torch.empty(n, dtype=torch.float32, device=dev)
-        n_acts = int(h.ltr_mlp_acts_floats(net, n))
-        if self._acts is None or self._acts.numel() < n_acts:
-            self._acts = torch.empty(n_acts, dtype=torch.float32, device=dev)
-        check(h.ltr_mlp_forward_save(net, _ptr(x2), n, _ptr(packed), int(dropout), seed, _ptr(k1), _ptr(k2),
-                                     _ptr(scores), _ptr(self._acts), self.grid, _stream()), "ltr_mlp_forward_save")
-        if self.loss_kind == LOSS_APPROXNDCG:
-            check(h.ltr_approxndcg_fwd_bwd(_ptr(scores), _ptr(yy), B, S, self.alpha, self.eps, self.pad, scale,
-                                           _ptr(self._slate), _ptr(ds), _stream()), "ltr_approxndcg_fwd_bwd")
-        elif self.loss_kind == LOSS_LISTNET:
-            check(h.ltr_listnet_fwd_bwd(_ptr(yy), _ptr(scores), B, S, int(self.apply_sigmoid), 1.0, _ptr(self._slate),
-                                        _ptr(ds), _stream()), "ltr_listnet_fwd_bwd")
-        else:
-            sid, kk, sigma, mu, eps, pad, lb = self.lambda_args
-            count = torch.empty(B, dtype=torch.float32, device=dev)
-            check(h.ltr_lambda_fwd_bwd(_ptr(scores), _ptr(yy), B, S, sid, kk, sigma, mu, eps, pad, lb, 1.0,
-                                       _ptr(self._slate), _ptr(count), _ptr(ds), _stream()), "ltr_lambda_fwd_bwd")
-        if self.kernel_events is not None:
-            self.kernel_events[0].record()
-        check(h.ltr_mlp_backward_saved(net, _ptr(x2), n, _ptr(packed), int(dropout), _ptr(self._acts), _ptr(ds),
-                                       _ptr(partials), self.grid, _stream()), "ltr_mlp_backward_saved")
-        if self.kernel_events is not None:
-            self.kernel_events[1].record()
-        self._reduce(fold, pf, partials, self.grid)
-        check(h.ltr_reduce_sum_f32(_ptr(self._slate), B, scale, self.flat.data_ptr() + 4 * self.info.n_params,
-                                   _stream()), "ltr_reduce_sum_f32")
-        if lambda_mean:
-            torch.sum(count, dim=0, keepdim=True, out=self._norm)
-            if not defer_norm:
-                self._divide_by_norm()
-        return self._loss_out
-
-    # ------------------------------------------------------------------------------------------ risk-sensitive losses
     def _risk_inputs(self, B, S, y_base, base_cols):
         """Host checks of a risk step's per-batch extras -> (yb [B, S, nb] or None, cache [B, C] or None, n_const)."""
         R = self.risk
@@ -670,37 +723,29 @@ class FusedRanker:
             yy = y.detach().to(torch.float32).contiguous()
             return risk_step.baseline_columns(self.risk, yy, self.risk.baselines(Q, S, y_base))
 
-    def _step_risk(self, h, x2, yy, B, S, dropout, seed, k1, k2, risk_in, world_batch, fold, pf, net, packed, partials):
-        """Scorer forward (activations saved) -> matrix rows + Jacobian -> [all_gather] -> tail -> scores gradient -> scorer backward
-        -> reduce (ltr_mi355x.risk_step)."""
+    def _step_risk(self, X, yy, risk_in, world_batch, keep1=None, keep2=None, seed=None, train=None):
+        """The chain with a risk loss in the middle: matrix rows + Jacobian -> [all_gather] -> tail -> scores gradient
+        (ltr_mi355x.risk_step)."""
         from . import risk_step as RS
-        R = self.risk
+        h, R = lib(), self.risk
+        B, S = yy.shape
         yb, cache, n_c = risk_in
         nsys = 1 + n_c
-        dev = self.device
-        n = B * S
         dp = (self.risk_group, self.risk_rank, self.risk_world)
-        mat, send, bmax = RS.matrix_rows(R, dev, dp, B, nsys, world_batch)
-        scores = torch.empty(n, dtype=torch.float32, device=dev)
-        jac = torch.empty(n, dtype=torch.float32, device=dev)
-        if B > 0:
-            n_acts = int(h.ltr_mlp_acts_floats(net, n))
-            if self._acts is None or self._acts.numel() < n_acts:
-                self._acts = torch.empty(n_acts, dtype=torch.float32, device=dev)
-            check(h.ltr_mlp_forward_save(net, _ptr(x2), n, _ptr(packed), int(dropout), seed, _ptr(k1), _ptr(k2),
-                                         _ptr(scores), _ptr(self._acts), self.grid, _stream()), "ltr_mlp_forward_save")
+        slot = self.flat[self.info.n_params:self.info.n_params + 1]
+        # Prepared before B is looked at: a rank without queries advances `_calls` here, while step_ragged leaves it alone on such a
+        # rank.  Nobody chose that difference; it is kept because the default dropout seeds of later steps depend on it.
+        rows = self._prepare(X, keep1, keep2, seed, train)
+        mat, send, bmax = RS.matrix_rows(R, self.device, dp, B, nsys, world_batch)
+
+        def loss_launches(scores, ds):
+            jac = torch.empty(B * S, dtype=torch.float32, device=self.device)
             RS.matrix(h, R, scores, yy, yb, cache, n_c, mat, jac)
-        coef, _dmat = RS.run_tail(h, R, dp, self.flat[self.info.n_params:self.info.n_params + 1], mat, send, bmax, B, nsys)
-        if B == 0:
+            coef, _dmat = RS.run_tail(h, R, dp, slot, mat, send, bmax, B, nsys)
+            RS.scores_grad(h, R, scores, yy, jac, coef, nsys, ds)
+
+        if B == 0:                                   # a rank without queries still joins the gather and runs the tail
+            RS.run_tail(h, R, dp, slot, mat, send, bmax, B, nsys)
             self.flat_grad.zero_()
-            return self._loss_out
-        ds = torch.empty(n, dtype=torch.float32, device=dev)
-        RS.scores_grad(h, R, scores, yy, jac, coef, nsys, ds)
-        if self.kernel_events is not None:
-            self.kernel_events[0].record()
-        check(h.ltr_mlp_backward_saved(net, _ptr(x2), n, _ptr(packed), int(dropout), _ptr(self._acts), _ptr(ds),
-                                       _ptr(partials), self.grid, _stream()), "ltr_mlp_backward_saved")
-        if self.kernel_events is not None:
-            self.kernel_events[1].record()
-        self._reduce(fold, pf, partials, self.grid)
-        return self._loss_out
+        else:
+            self._chain(rows, loss_launches)

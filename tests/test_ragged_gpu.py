@@ -482,3 +482,33 @@ def test_step_ragged_edge_cases_and_risk_losses(dev):
         rr = FusedRanker(net, loss=name)
         with pytest.raises(NotImplementedError, match="FusedRanker.step"):
             rr.step_ragged(x.to(dev), y.to(dev), sl)
+
+
+@pytest.mark.parametrize("loss,red", [("approxNDCG", "sum"), ("listnet", "sum"), ("lambdaLoss", "sum"), ("lambdaLoss", "mean")])
+@pytest.mark.parametrize("S", [17, 257])
+@pytest.mark.parametrize("kind", ["double_train", "triple", "fc"])
+def test_equal_lengths_are_the_rectangular_listwise_step_bits(kind, S, loss, red, dev):
+    """Q queries of one length: `step` on [Q, S, F] and `step_ragged` on the same rows leave the same bits in `flat_ext` -- the
+    listwise counterpart of test_ragged_risk_gpu.py::test_equal_lengths_are_the_rectangular_step_bits.  Neither length is a
+    one-launch one, so both run the ranker's chain; the loss launches are bitwise equal at these tiers
+    (test_equal_lengths_are_the_rectangular_bits), and 257 is the first length of lambdaLoss's 512 tier."""
+    from ltr_mi355x.scorer import FusedRanker
+    Q, F = 5, 136
+    if kind == "fc":
+        from test_linear_fused_gpu import _model
+        net = _model(dev)
+        net.eval()
+    else:
+        net, _ = _make("triple" if kind == "triple" else "double", dev, 31)
+        net.train(kind == "double_train")
+    extra = dict(weighing_scheme="ndcgLoss2PP_scheme", reduction=red) if loss == "lambdaLoss" else {}
+    ranker = FusedRanker(net, loss=loss, **extra)
+    x, y = _step_data([S] * Q, 700 + S, F)
+    X, Y = x.to(dev), y.to(dev)
+    kw = dict(seed=4321) if kind == "double_train" else {}
+    ranker.step(X.view(Q, S, F), Y.view(Q, S), **kw)
+    a = ranker.flat_ext.clone()
+    assert torch.isfinite(a).all() and float(ranker.flat_grad.abs().max()) > 0.0
+    ranker.flat_ext.zero_()
+    ranker.step_ragged(X, Y, _slates([S] * Q, dev), **kw)
+    assert torch.equal(a, ranker.flat_ext)

@@ -619,3 +619,38 @@ def test_other_dropout_probabilities(p, S, dev):
     net.dropout.p = 1.5
     with pytest.raises(ValueError):
         net(x.to(dev), None, None)
+
+
+def test_default_seed_counter_across_step_kinds(dev):
+    """The default dropout seed of the n-th EXECUTED step is next_seed(n): a chain step, the one-launch step and step_ragged draw from one
+    counter, and a step the empty batch answers leaves it alone.  Ranker A runs default-seeded, ranker B (a deep copy of the net) the
+    same non-empty steps with next_seed(0), next_seed(1), next_seed(2) spelled out: the same bits in `flat` after each."""
+    import copy
+    from ltr_mi355x import scorer
+    from ltr_mi355x.ragged import RaggedSlates
+    from ltr_mi355x.scorer import FusedRanker
+    net_a, _ = _make("double", dev, 23)
+    net_a.train()
+    net_b = copy.deepcopy(net_a)
+    A, B_ = FusedRanker(net_a, loss="approxNDCG"), FusedRanker(net_b, loss="approxNDCG")
+    B = 3
+    gen = torch.Generator().manual_seed(2300)
+
+    def batch(S):
+        return torch.randn(B, S, 136, generator=gen).to(dev), torch.randint(0, 5, (B, S), generator=gen).float().to(dev)
+
+    x5, y5 = batch(5)
+    x32, y32 = batch(32)
+    xr, yr = torch.randn(10, 136, generator=gen).to(dev), torch.randint(0, 5, (10,), generator=gen).float().to(dev)
+    sl = RaggedSlates(np.array([0, 3, 10], dtype=np.int64), device=dev)
+
+    A.step(x5, y5)
+    B_.step(x5, y5, seed=scorer.next_seed(0))
+    assert torch.equal(A.flat, B_.flat) and float(A.flat_grad.abs().max()) > 0.0
+    A.step(x5[:0], y5[:0])                           # answered by the prelude: no seed drawn
+    A.step_ragged(xr, yr, sl)
+    B_.step_ragged(xr, yr, sl, seed=scorer.next_seed(1))
+    assert torch.equal(A.flat, B_.flat) and float(A.flat_grad.abs().max()) > 0.0
+    A.step(x32, y32)
+    B_.step(x32, y32, seed=scorer.next_seed(2))
+    assert torch.equal(A.flat, B_.flat) and float(A.flat_grad.abs().max()) > 0.0
