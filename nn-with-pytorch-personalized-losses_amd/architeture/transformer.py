@@ -198,7 +198,7 @@ def _attention_general(query, key, value, mask, dropout):
 def attention(query, key, value, mask=None, dropout=None):
     """transformer.py:145-164: query / key / value [batch, heads, slate, d_k] -> (output [batch, heads, slate, d_k], p_attn
     [batch, heads, slate, slate]).  `dropout`: None or an nn.Dropout module (applied to p_attn when it is in training mode).
-    The output carries the analytic backward (ltr_enc_attention_bwd); p_attn is returned detached.  Key / value sets shaped unlike the
+    The output carries the analytic backward (ltr_enc_attention_bwd_lse); p_attn is returned detached.  Key / value sets shaped unlike the
     query set and masks other than one flag per document take the reference's formulation on the device (_attention_general)."""
     B = _blocks()
     nb, h, S, dk = query.shape

@@ -1,7 +1,7 @@
 """The building blocks of architeture/transformer.py and architeture/multiLayer.py called ON THEIR OWN (outside an LTRModel):
-each is one torch.autograd.Function over the same C-ABI entry points the fused network uses (include/ltr_encoder.h), with
-the same arithmetic -- bf16 operands on the matrix cores, fp32 accumulation / statistics / gradients -- and an analytic
-backward that also returns the gradient w.r.t. the block's input.
+each is one torch.autograd.Function over the same launch chains and kernel wrappers the fused network uses (ltr_mi355x/encoder.py;
+this module makes no C-ABI call of its own), with the same arithmetic -- bf16 operands on the matrix cores, fp32 accumulation /
+statistics / gradients -- and an analytic backward that also returns the gradient w.r.t. the block's input.
 
     features(...)           FCModel.forward (multiLayer.py:36-46), EncoderLayer.forward (transformer.py:134-142),
                             Encoder.forward (:45-59), LTRModel.prepare_for_output (multiLayer.py:64-72)
@@ -16,10 +16,8 @@ Device tensors only; there is no CPU fallback."""
 import torch
 
 from . import encoder as E
-from ._lib import check, lib
-from .functional import _ptr, _stream, require_device
+from .functional import require_device
 
-_U16 = E._U16
 _calls = [0]
 
 
@@ -53,7 +51,7 @@ def slate_mask(mask, B, S, device):
     if mask.numel() != B * S:
         raise NotImplementedError(f"only per-document padding masks ([batch, slate], optionally with singleton head / query axes) "
                                   f"are built on the HIP path, got {tuple(mask.shape)} for batch {B}, slate {S}")
-    return (mask.to(device) == 1).to(torch.uint8).contiguous().view(B, S)
+    return E.padding_mask_u8(mask, B, S, device)
 
 
 # ----------------------------------------------------------------------------------------------------- FC / encoder bodies
@@ -187,14 +185,8 @@ class LinearFn(torch.autograd.Function):
             g = dy.detach().to(torch.float32).contiguous().view(T, N)
             if Np != N:
                 g = torch.cat([g, torch.zeros((T, Np - N), dtype=torch.float32, device=dev)], 1).contiguous()
-            dy16, gb = E._drop_cast_colsum(g, T, Np, 0.0, 0, 0)
-            gW = E._weight_grad(dy16, ctx.x16, T, Np, K)
-            dx = None
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty((T, K), dtype=torch.float32, device=dev)
-                E.gemm(dy16, ctx.w16, T, K, Np, b_kmajor=True, Cf=dx)
-                dx = dx.view(xshape).to(xdt)
-        return dx, gW[:N].to(wdt), gb[:N].to(bdt)
+            dx, gW, gb = E.linear_bwd(g, ctx.x16, ctx.w16, T, Np, K, 0.0, 0, 0, ctx.needs_input_grad[0])
+        return None if dx is None else dx.view(xshape).to(xdt), gW[:N].to(wdt), gb[:N].to(bdt)
 
 
 def linear(x, W, b):
@@ -212,14 +204,13 @@ class ScoreLinearFn(torch.autograd.Function):
         xf = _tokens(x, d)
         T = xf.shape[0]
         ctx.meta = (x.dtype, tuple(x.shape), W.dtype, b.dtype, d)
-        out = torch.empty(T, dtype=torch.float32, device=x.device)
         ctx.empty = T == 0
-        if T:
-            wf, bf = _f32(W), _f32(b)
-            with torch.cuda.device(x.device):
-                check(lib().ltr_enc_score_fwd(_ptr(xf), None, None, _ptr(wf), _ptr(bf), T, d, E.LN_EPS, 0, _ptr(out), _stream()),
-                      "ltr_enc_score_fwd")
-            ctx.save_for_backward(xf, wf)       # fp32 contiguous x / W: the caller's own tensors (version-checked at unpack)
+        if T == 0:
+            return torch.empty((*x.shape[:-1], 1), dtype=torch.float32, device=x.device)
+        wf, bf = _f32(W), _f32(b)
+        with torch.cuda.device(x.device):
+            out = E.score_fwd(xf, None, None, wf, bf, T, d, False)
+        ctx.save_for_backward(xf, wf)           # fp32 contiguous x / W: the caller's own tensors (version-checked at unpack)
         return out.view(*x.shape[:-1], 1)
 
     @staticmethod
@@ -232,12 +223,8 @@ class ScoreLinearFn(torch.autograd.Function):
         T = xf.shape[0]
         with torch.cuda.device(dev):
             ds = dscores.detach().to(torch.float32).contiguous().view(T)
-            nblk = max(1, min(E._NBLK, (T + 3) // 4))
-            dx = torch.empty((T, d), dtype=torch.float32, device=dev)
-            parts = torch.empty((nblk, 3 * d + 8), dtype=torch.float32, device=dev)
-            check(lib().ltr_enc_score_bwd(_ptr(xf), None, None, _ptr(wf), _ptr(ds), T, d, E.LN_EPS, 0, _ptr(dx), _ptr(parts), nblk,
-                                          _stream()), "ltr_enc_score_bwd")
-            g = E.sum_partials(parts, nblk, 3 * d + 8)
+            dx, parts = E.score_bwd(xf, None, None, wf, ds, T, d, False)
+            g = E.sum_partials(parts, *parts.shape)
         return dx.view(xshape).to(xdt), g[2 * d:3 * d].view(1, d).to(wdt), g[3 * d:3 * d + 1].to(bdt)
 
 
@@ -271,15 +258,7 @@ class MultiHeadFn(torch.autograd.Function):
             w16 = E.cast_bf16(torch.cat([_f32(Wq).reshape(-1), _f32(Wk).reshape(-1), _f32(Wv).reshape(-1), _f32(Wo).reshape(-1)]))
             wqkv, wo16 = w16[:3 * d * d].view(3 * d, d), w16[3 * d * d:].view(d, d)
             bqkv = torch.cat([_f32(bq), _f32(bk), _f32(bv)])
-            qkv = torch.empty((T, 3 * d), dtype=_U16, device=dev)
-            if same:
-                E.gemm(srcs[0], wqkv, T, 3 * d, d, Cb=qkv, bias=bqkv)
-            else:
-                for j in range(3):
-                    E.gemm(srcs[j], wqkv[j * d:(j + 1) * d], T, d, d, Cb=qkv[:, j * d:], ldc=3 * d, bias=bqkv[j * d:(j + 1) * d])
-            ctxb, lse = E.attention_fwd(qkv, mask_u8, B, S, h, dk, p, seed, 0)
-            out = torch.empty((T, d), dtype=torch.float32, device=dev)
-            E.gemm(ctxb, wo16, T, d, d, Cf=out, bias=_f32(bo))
+            qkv, ctxb, lse, out = E.attention_sublayer_fwd(srcs, wqkv, wo16, bqkv, _f32(bo), mask_u8, B, S, h, dk, p, seed, 0)
         ctx.saved = (srcs, wqkv, wo16, qkv, ctxb, lse)
         ctx.save_for_backward(mask_u8)          # the caller's tensor (version-checked at unpack)
         return out.view(B, S, d)
@@ -298,34 +277,9 @@ class MultiHeadFn(torch.autograd.Function):
         T, dk = B * S, d // h
         with torch.cuda.device(dev):
             g = dout.detach().to(torch.float32).contiguous().view(T, d)
-            dy16, gbo = E._drop_cast_colsum(g, T, d, 0.0, 0, 0)
-            gWo = E._weight_grad(dy16, ctxb, T, d, d)
-            dctx = torch.empty((T, d), dtype=_U16, device=dev)
-            E.gemm(dy16, wo16, T, d, d, b_kmajor=True, Cb=dctx)
-            with E.forward_epoch(ctx.epoch):
-                dqkv = E.attention_bwd(qkv, ctxb, dctx, lse, mask_u8, B, S, h, dk, p, seed, 0)
-            gbqkv = E._colsum(dqkv, T, 3 * d)
-            need = ctx.needs_input_grad[4:7]
-            if same:
-                gW = E._weight_grad(dqkv, srcs[0], T, 3 * d, d)
-                gWs = [gW[j * d:(j + 1) * d] for j in range(3)]
-                dins = [None, None, None]
-                if need[0]:
-                    dx = torch.empty((T, d), dtype=torch.float32, device=dev)
-                    E.gemm(dqkv, wqkv, T, d, 3 * d, b_kmajor=True, Cf=dx)
-                    dins[0] = dx.view(B, S, d).to(in_dts[0])
-            else:
-                gWs, dins = [], []
-                for j in range(3):
-                    sl = dqkv[:, j * d:]
-                    gWs.append(E._weight_grad(sl, srcs[j], T, d, d, lda=3 * d))
-                    dx = None
-                    if need[j]:
-                        dx = torch.empty((T, d), dtype=torch.float32, device=dev)
-                        E.gemm(sl, wqkv[j * d:(j + 1) * d], T, d, d, lda=3 * d, b_kmajor=True, Cf=dx)
-                        dx = dx.view(B, S, d).to(in_dts[j])
-                    dins.append(dx)
-        gp = [gWs[0], gbqkv[:d], gWs[1], gbqkv[d:2 * d], gWs[2], gbqkv[2 * d:], gWo, gbo]
+            gp, dins = E.attention_sublayer_bwd(g, srcs, wqkv, wo16, qkv, ctxb, lse, mask_u8, B, S, h, dk, p, seed, 0, ctx.needs_input_grad[4:7],
+                                                epoch=ctx.epoch)
+            dins = [None if dx is None else dx.view(B, S, d).to(t) for dx, t in zip(dins, in_dts)] + [None] * (3 - len(dins))
         return (None, None, None, None, dins[0], dins[1], dins[2], None, *[g_.to(t) for g_, t in zip(gp, p_dts)])
 
 
@@ -373,10 +327,7 @@ def attention_probs(query, key, mask_u8, p, seed):
         packed = torch.cat([query.detach().to(torch.float32).transpose(1, 2).reshape(T, d),
                             key.detach().to(torch.float32).transpose(1, 2).reshape(T, d), zeros], 1).contiguous()
         qkv = E.cast_bf16(packed)
-        probs = torch.empty((B, h, S, S), dtype=torch.float32, device=dev)
-        check(lib().ltr_enc_attention_probs(_ptr(qkv), _ptr(mask_u8), B, S, h, dk, float(p), int(seed), 0, _ptr(probs), _stream()),
-              "ltr_enc_attention_probs")
-    return probs
+        return E.attention_probs(qkv, mask_u8, B, S, h, dk, p, seed, 0)
 
 
 # ----------------------------------------------------------------------------------------------------- feed-forward
@@ -397,10 +348,7 @@ class FeedForwardFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             x16 = E.cast_bf16(xf)
             w116, w216 = E.cast_bf16(_f32(W1)), E.cast_bf16(_f32(W2))
-            hid = torch.empty((T, dff), dtype=_U16, device=dev)
-            E.gemm(x16, w116, T, dff, d, Cb=hid, bias=_f32(b1), relu=True, drop_p=p, seed=seed, drop_stream=2)
-            out = torch.empty((T, d), dtype=torch.float32, device=dev)
-            E.gemm(hid, w216, T, d, dff, Cf=out, bias=_f32(b2))
+            hid, out = E.ffn_gemm_fwd(x16, w116, _f32(b1), w216, _f32(b2), T, d, dff, p, seed, 2, 1)     # never split-K: ks = 1
         ctx.saved = (x16, w116, w216, hid)
         return out.view(x.shape)
 
@@ -416,15 +364,5 @@ class FeedForwardFn(torch.autograd.Function):
         T = x16.shape[0]
         with torch.cuda.device(dev):
             g = dout.detach().to(torch.float32).contiguous().view(T, d)
-            dy16, gb2 = E._drop_cast_colsum(g, T, d, 0.0, 0, 0)
-            gW2 = E._weight_grad(dy16, hid, T, d, dff)
-            dz1 = torch.empty((T, dff), dtype=_U16, device=dev)
-            E.gemm(dy16, w216, T, dff, d, b_kmajor=True, Cb=dz1, gate=hid, gate_scale=1.0 / (1.0 - p))
-            gb1 = E._colsum(dz1, T, dff)
-            gW1 = E._weight_grad(dz1, x16, T, dff, d)
-            dx = None
-            if ctx.needs_input_grad[2]:
-                dx = torch.empty((T, d), dtype=torch.float32, device=dev)
-                E.gemm(dz1, w116, T, d, dff, b_kmajor=True, Cf=dx)
-                dx = dx.view(xshape).to(xdt)
-        return None, None, dx, gW1.to(dts[0]), gb1.to(dts[1]), gW2.to(dts[2]), gb2.to(dts[3])
+            dx, gW1, gb1, gW2, gb2 = E.ffn_gemm_bwd(g, x16, hid, w116, w216, T, d, dff, p, 1, want_dx=ctx.needs_input_grad[2])
+        return None, None, None if dx is None else dx.view(xshape).to(xdt), gW1.to(dts[0]), gb1.to(dts[1]), gW2.to(dts[2]), gb2.to(dts[3])

@@ -240,6 +240,13 @@ def attention_fwd(qkv, mask_u8, B, S, h, dk, p, seed, stream_id):
     return ctxb, lse
 
 
+def attention_probs(qkv, mask_u8, B, S, h, dk, p, seed, stream_id):
+    probs = torch.empty((B, h, S, S), dtype=torch.float32, device=qkv.device)
+    check(lib().ltr_enc_attention_probs(_ptr(qkv), _ptr(mask_u8), B, S, h, dk, float(p), int(seed), int(stream_id), _ptr(probs),
+                                        _stream()), "ltr_enc_attention_probs")
+    return probs
+
+
 def attention_bwd(qkv, ctxb, dctx, lse, mask_u8, B, S, h, dk, p, seed, stream_id):
     dqkv = torch.empty((B * S, 3 * h * dk), dtype=_U16, device=qkv.device)
     check(lib().ltr_enc_attention_bwd_lse(_ptr(qkv), _ptr(ctxb), _ptr(dctx), _ptr(lse), _ptr(mask_u8), B, S, h, dk, float(p), int(seed),
@@ -284,6 +291,129 @@ def ffn_bwd(n2, w1, b1, w2, dy, T, d, dff, p, seed, s_hidden):
                                   _ptr(p1), _ptr(p2), _ptr(pb), _stream()), "ltr_enc_ffn_bwd_w")
     return (dn2, sum_partials(p1, nsplit, dff * d).view(dff, d), sum_partials(p2, nsplit, d * dff).view(d, dff),
             sum_partials(pb, nsplit, dff))
+
+
+# ---- the launch chains of the sublayers, written once: the fused network (_run_forward / _body_backward) and the stand-alone
+# blocks (ltr_mi355x.blocks) both walk these.  Activations are bf16 [T, width], incoming gradients and residuals fp32.
+#   residual, out_drop   what SublayerConnection adds around a sublayer, which only the network has: the residual-stream tensor and
+#                        (p, seed, stream id) of the dropout on the sublayer's output
+#   want / want_dx       whether to launch the input-gradient GEMM (None is returned in its place otherwise)
+#   ks                   split-K factor of the FFN's two (T, d, d_ff) GEMMs (few tiles, a long k loop): with ks > 1 they write ks
+#                        partials, reduced by splitk_epilogue (bias + dropout + residual there) and sum_partials
+# gemm / splitk_epilogue are looked up at call time (tests wrap them).
+NO_DROP = (0.0, 0, 0)
+
+
+def attention_sublayer_fwd(srcs, wqkv, wo16, bqkv, bo, mask_u8, B, S, h, dk, p, seed, stream_id, residual=None, out_drop=NO_DROP):
+    """out = residual + drop(attention(srcs) Wo^T + bo) for srcs = [x] (query = key = value: one QKV GEMM) or [query, key, value]
+    (three GEMMs into the column blocks of qkv).  Returns (qkv, ctxb, lse, out)."""
+    T, d = B * S, h * dk
+    qkv = torch.empty((T, 3 * d), dtype=_U16, device=srcs[0].device)
+    if len(srcs) == 1:
+        gemm(srcs[0], wqkv, T, 3 * d, d, Cb=qkv, bias=bqkv)
+    else:
+        for j in range(3):
+            gemm(srcs[j], wqkv[j * d:(j + 1) * d], T, d, d, Cb=qkv[:, j * d:], ldc=3 * d, bias=bqkv[j * d:(j + 1) * d])
+    ctxb, lse = attention_fwd(qkv, mask_u8, B, S, h, dk, p, seed, stream_id)
+    out = torch.empty((T, d), dtype=torch.float32, device=qkv.device)
+    gemm(ctxb, wo16, T, d, d, Cf=out, bias=bo, residual=residual, drop_p=out_drop[0], seed=out_drop[1], drop_stream=out_drop[2])
+    return qkv, ctxb, lse, out
+
+
+def attention_sublayer_bwd(dout, srcs, wqkv, wo16, qkv, ctxb, lse, mask_u8, B, S, h, dk, p, seed, stream_id, want, out_drop=NO_DROP, epoch=None):
+    """([dWq, dbq, dWk, dbk, dWv, dbv, dWo, dbo], [gradient w.r.t. srcs[j] if want[j]]).  `epoch`: the forward's epoch_save slot when
+    the caller is not inside forward_epoch itself."""
+    T, d = B * S, h * dk
+    dev = dout.device
+    dyo, gbo = _drop_cast_colsum(dout, T, d, *out_drop)
+    gWo = _weight_grad(dyo, ctxb, T, d, d)
+    dctx = torch.empty((T, d), dtype=_U16, device=dev)
+    gemm(dyo, wo16, T, d, d, b_kmajor=True, Cb=dctx)
+    with forward_epoch(epoch):
+        dqkv = attention_bwd(qkv, ctxb, dctx, lse, mask_u8, B, S, h, dk, p, seed, stream_id)
+    gbqkv = _colsum(dqkv, T, 3 * d)
+    dins = [None] * len(srcs)
+    if len(srcs) == 1:
+        gW = _weight_grad(dqkv, srcs[0], T, 3 * d, d)
+        gWs = (gW[:d], gW[d:2 * d], gW[2 * d:])
+        if want[0]:
+            dins[0] = torch.empty((T, d), dtype=torch.float32, device=dev)
+            gemm(dqkv, wqkv, T, d, 3 * d, b_kmajor=True, Cf=dins[0])
+    else:
+        gWs = []
+        for j in range(3):
+            sl = dqkv[:, j * d:]
+            gWs.append(_weight_grad(sl, srcs[j], T, d, d, lda=3 * d))
+            if want[j]:
+                dins[j] = torch.empty((T, d), dtype=torch.float32, device=dev)
+                gemm(sl, wqkv[j * d:(j + 1) * d], T, d, d, lda=3 * d, b_kmajor=True, Cf=dins[j])
+    return [gWs[0], gbqkv[:d], gWs[1], gbqkv[d:2 * d], gWs[2], gbqkv[2 * d:], gWo, gbo], dins
+
+
+def ffn_gemm_fwd(x16, w116, b1, w216, b2, T, d, dff, p, seed, s_hidden, ks, residual=None, out_drop=NO_DROP):
+    """The GEMM-path FFN: (hid = drop(relu(x W1^T + b1)), out = residual + drop(hid W2^T + b2))."""
+    dev = x16.device
+    hid = torch.empty((T, dff), dtype=_U16, device=dev)
+    gemm(x16, w116, T, dff, d, Cb=hid, bias=b1, relu=True, drop_p=p, seed=seed, drop_stream=s_hidden)
+    out = torch.empty((T, d), dtype=torch.float32, device=dev)
+    if ks > 1:
+        parts = torch.empty((ks, T, d), dtype=torch.float32, device=dev)
+        gemm(hid, w216, T, d, dff, Cf=parts, splits=ks)
+        splitk_epilogue(parts, ks, T, d, b2, out_drop[0], out_drop[1], out_drop[2], residual, out)
+    else:
+        gemm(hid, w216, T, d, dff, Cf=out, bias=b2, residual=residual, drop_p=out_drop[0], seed=out_drop[1], drop_stream=out_drop[2])
+    return hid, out
+
+
+def ffn_gemm_bwd(dout, x16, hid, w116, w216, T, d, dff, p, ks, want_dx=True, out_drop=NO_DROP):
+    """(dx, dW1, db1, dW2, db2) of ffn_gemm_fwd, launched in the order dy, dW2, dz1 (gated by hid), db1, dW1, dx."""
+    dev = dout.device
+    dy, gb2 = _drop_cast_colsum(dout, T, d, *out_drop)
+    gW2 = _weight_grad(dy, hid, T, d, dff)
+    dz1 = torch.empty((T, dff), dtype=_U16, device=dev)
+    gemm(dy, w216, T, dff, d, b_kmajor=True, Cb=dz1, gate=hid, gate_scale=1.0 / (1.0 - p))
+    gb1 = _colsum(dz1, T, dff)
+    gW1 = _weight_grad(dz1, x16, T, dff, d)
+    dx = torch.empty((T, d), dtype=torch.float32, device=dev) if want_dx else None
+    if want_dx and ks > 1:
+        parts = torch.empty((ks, T, d), dtype=torch.float32, device=dev)
+        gemm(dz1, w116, T, d, dff, b_kmajor=True, Cf=parts, splits=ks)
+        sum_partials(parts, ks, T * d, out=dx.view(-1))
+    elif want_dx:
+        gemm(dz1, w116, T, d, dff, b_kmajor=True, Cf=dx)
+    return dx, gW1, gb1, gW2, gb2
+
+
+def linear_bwd(dy, x16, w16, T, n_out, n_in, p, seed, stream_id, want_dx):
+    """(dx, dW, db) of y = drop(x W^T + b)."""
+    dy16, gb = _drop_cast_colsum(dy, T, n_out, p, seed, stream_id)
+    gW = _weight_grad(dy16, x16, T, n_out, n_in)
+    dx = torch.empty((T, n_in), dtype=torch.float32, device=dy.device) if want_dx else None
+    if want_dx:
+        gemm(dy16, w16, T, n_in, n_out, b_kmajor=True, Cf=dx)
+    return dx, gW, gb
+
+
+def score_fwd(x, a, b, w, bias, T, d, with_norm, shape=None):
+    """scores fp32 ([T], or `shape` of T elements) = w . norm(x[t]) + bias (norm: the encoder's final LayerNorm (a, b) if with_norm)."""
+    scores = torch.empty(T if shape is None else shape, dtype=torch.float32, device=x.device)
+    check(lib().ltr_enc_score_fwd(_ptr(x), _ptr(a), _ptr(b), _ptr(w), _ptr(bias), T, d, LN_EPS, 1 if with_norm else 0, _ptr(scores),
+                                  _stream()), "ltr_enc_score_fwd")
+    return scores
+
+
+def score_bwd(x, a, b, w, ds, T, d, with_norm):
+    """(dx, partial rows [nblk, 3d + 8] of d a | d b | d w | d bias: sum_partials(parts, *parts.shape) where the caller's reduce belongs)."""
+    nblk = max(1, min(_NBLK, (T + 3) // 4))
+    dx = torch.empty((T, d), dtype=torch.float32, device=x.device)
+    parts = torch.empty((nblk, 3 * d + 8), dtype=torch.float32, device=x.device)
+    check(lib().ltr_enc_score_bwd(_ptr(x), _ptr(a), _ptr(b), _ptr(w), _ptr(ds), T, d, LN_EPS, 1 if with_norm else 0, _ptr(dx), _ptr(parts),
+                                  nblk, _stream()), "ltr_enc_score_bwd")
+    return dx, parts
+
+
+def padding_mask_u8(mask, B, S, device):      # B * S padding flags (1 = padded) as the kernels take them: uint8 [B][S]
+    return (mask.to(device) == 1).to(torch.uint8).contiguous().view(B, S)
 
 
 class EncoderSpec:
@@ -380,7 +510,7 @@ def _run_forward(spec, x, mask, seed, training, params):
     d = spec.d_model
     # ---- Encoder blocks (transformer.py:44-59, 132-142)
     if spec.has_encoder:
-        mask_u8 = (mask.to(dev) == 1).to(torch.uint8).contiguous().view(B, S)
+        mask_u8 = padding_mask_u8(mask, B, S, dev)
         st["mask_u8"] = mask_u8
         h, dk, dff = spec.heads, spec.dk, spec.d_ff
         st["fused_ffn"] = fused_ffn_enabled(d, dff, T)
@@ -399,26 +529,15 @@ def _run_forward(spec, x, mask, seed, training, params):
             st["enc_w16"].append((wqkv, wo16, w116, w216))
             x0 = stream_x
             n1 = layernorm_fwd(x0, a1, b1n, T, d, LN_EPS, 0)
-            qkv = torch.empty((T, 3 * d), dtype=_U16, device=dev)
-            gemm(n1, wqkv, T, 3 * d, d, Cb=qkv, bias=bqkv)
-            ctxb, lse = attention_fwd(qkv, mask_u8, B, S, h, dk, p_enc, seed, stream_attn(l))
-            x1 = torch.empty((T, d), dtype=torch.float32, device=dev)
-            gemm(ctxb, wo16, T, d, d, Cf=x1, bias=bo, residual=x0, drop_p=p_enc, seed=seed, drop_stream=stream_attn_out(l))
+            qkv, ctxb, lse, x1 = attention_sublayer_fwd([n1], wqkv, wo16, bqkv, bo, mask_u8, B, S, h, dk, p_enc, seed, stream_attn(l),
+                                                        residual=x0, out_drop=(p_enc, seed, stream_attn_out(l)))
             n2 = layernorm_fwd(x1, a2, b2n, T, d, LN_EPS, 0)
             if st["fused_ffn"]:
                 hid = None
                 x2 = ffn_fwd(n2, w116, b1, w216, b2, x1, T, d, dff, p_enc, seed, stream_ffn_hidden(l), stream_ffn_out(l))
             else:
-                hid = torch.empty((T, dff), dtype=_U16, device=dev)
-                gemm(n2, w116, T, dff, d, Cb=hid, bias=b1, relu=True, drop_p=p_enc, seed=seed, drop_stream=stream_ffn_hidden(l))
-                x2 = torch.empty((T, d), dtype=torch.float32, device=dev)
-                ks = _small_step_splits(T, d, dff)
-                if ks > 1:          # 32 output tiles, 32 k-steps each: split-K partials, then bias + dropout + residual in the reduce
-                    parts = torch.empty((ks, T, d), dtype=torch.float32, device=dev)
-                    gemm(hid, w216, T, d, dff, Cf=parts, splits=ks)
-                    splitk_epilogue(parts, ks, T, d, b2, p_enc, seed, stream_ffn_out(l), x1, x2)
-                else:
-                    gemm(hid, w216, T, d, dff, Cf=x2, bias=b2, residual=x1, drop_p=p_enc, seed=seed, drop_stream=stream_ffn_out(l))
+                hid, x2 = ffn_gemm_fwd(n2, w116, b1, w216, b2, T, d, dff, p_enc, seed, stream_ffn_hidden(l), _small_step_splits(T, d, dff),
+                                       residual=x1, out_drop=(p_enc, seed, stream_ffn_out(l)))
             st["layers"].append((x0, n1, qkv, ctxb, x1, n2, hid, lse))
             stream_x = x2
     st["xin"], st["prm"], st["final_x"] = xin, prm, stream_x
@@ -444,12 +563,9 @@ class EncoderScores(torch.autograd.Function):
             B, S, _ = st["dims"]
             prm = st["prm"]
             fa, fb = (prm[-4], prm[-3]) if spec.has_encoder else (None, None)
-            ow, ob = prm[-2], prm[-1]
-            if ow.shape[0] != 1:
+            if prm[-2].shape[0] != 1:
                 raise NotImplementedError("OutputLayer with d_output > 1 is not built on the HIP path")
-            scores = torch.empty((B, S), dtype=torch.float32, device=x.device)
-            check(lib().ltr_enc_score_fwd(_ptr(st["final_x"]), _ptr(fa), _ptr(fb), _ptr(ow), _ptr(ob), B * S, spec.d_model, LN_EPS,
-                                          1 if spec.has_encoder else 0, _ptr(scores), _stream()), "ltr_enc_score_fwd")
+            scores = score_fwd(st["final_x"], fa, fb, prm[-2], prm[-1], B * S, spec.d_model, spec.has_encoder, shape=(B, S))
         ctx.spec, ctx.seed, ctx.st = spec, int(seed), hand_over(ctx, st)
         return scores
 
@@ -466,13 +582,9 @@ class EncoderScores(torch.autograd.Function):
             ds = dscores.detach().to(torch.float32).contiguous().view(T)
             # ---- output layer (+ final norm)
             fa, fb = (prm[-4], prm[-3]) if spec.has_encoder else (None, None)
-            nblk = max(1, min(_NBLK, (T + 3) // 4))
-            dx = torch.empty((T, d), dtype=torch.float32, device=dev)
-            parts = torch.empty((nblk, 3 * d + 8), dtype=torch.float32, device=dev)
-            check(lib().ltr_enc_score_bwd(_ptr(st["final_x"]), _ptr(fa), _ptr(fb), _ptr(prm[-2]), _ptr(ds), T, d, LN_EPS,
-                                          1 if spec.has_encoder else 0, _ptr(dx), _ptr(parts), nblk, _stream()), "ltr_enc_score_bwd")
+            dx, parts = score_bwd(st["final_x"], fa, fb, prm[-2], ds, T, d, spec.has_encoder)
             with deferred_reductions():
-                grads = _with_tail(spec, _body_backward(spec, seed, st, dx)[0], sum_partials(parts, nblk, 3 * d + 8))
+                grads = _with_tail(spec, _body_backward(spec, seed, st, dx)[0], sum_partials(parts, *parts.shape))
         out = [g if g is None else g.to(dt).reshape(p.shape) for g, dt, p in zip(grads, ctx.param_dtypes, prm)]
         return (None, None, None, None, None, *out)
 
@@ -512,8 +624,6 @@ def _body_backward(spec, seed, st, dx, want_dx=False):
     T = B * S
     p_fc, p_enc = st["p"]
     prm = st["prm"]
-    fc_w16, enc_w16 = st["fc_w16"], st["enc_w16"]
-    dev = dx.device
     d = spec.d_model
     n_fc0 = 2 if spec.input_norm else 0
     n_fc = n_fc0 + 2 * len(spec.fc_sizes)
@@ -523,52 +633,30 @@ def _body_backward(spec, seed, st, dx, want_dx=False):
         for l in reversed(range(spec.n_layers)):
             base = n_fc + 16 * l
             a1, _, Wq, _, _, _, _, _, Wo, _, a2, _, W1, _, W2, _ = prm[base:base + 16]
-            wqkv, wo16, w116, w216 = enc_w16[l]
+            wqkv, wo16, w116, w216 = st["enc_w16"][l]
             x0, n1, qkv, ctxb, x1, n2, hid, lse = st["layers"][l]
             # FFN sublayer: x2 = x1 + drop(hid W2^T + b2)
-            dy2, gb2 = _drop_cast_colsum(dx, T, d, p_enc, seed, stream_ffn_out(l))
             if st["fused_ffn"]:
+                dy2, gb2 = _drop_cast_colsum(dx, T, d, p_enc, seed, stream_ffn_out(l))
                 dn2, gW1, gW2, gb1 = ffn_bwd(n2, w116, prm[base + 13], w216, dy2, T, d, dff, p_enc, seed, stream_ffn_hidden(l))
             else:
-                gW2 = _weight_grad(dy2, hid, T, d, dff)
-                dz1 = torch.empty((T, dff), dtype=_U16, device=dev)
-                gemm(dy2, w216, T, dff, d, b_kmajor=True, Cb=dz1, gate=hid, gate_scale=1.0 / (1.0 - p_enc))
-                gb1 = _colsum(dz1, T, dff)
-                gW1 = _weight_grad(dz1, n2, T, dff, d)
-                dn2 = torch.empty((T, d), dtype=torch.float32, device=dev)
-                ks = _small_step_splits(T, d, dff)
-                if ks > 1:          # few output tiles and a long k loop: split-K partials + one reduce (32 workgroups -> 32 ks)
-                    parts = torch.empty((ks, T, d), dtype=torch.float32, device=dev)
-                    gemm(dz1, w116, T, d, dff, b_kmajor=True, Cf=parts, splits=ks)
-                    sum_partials(parts, ks, T * d, out=dn2.view(-1))
-                else:
-                    gemm(dz1, w116, T, d, dff, b_kmajor=True, Cf=dn2)
+                dn2, gW1, gb1, gW2, gb2 = ffn_gemm_bwd(dx, n2, hid, w116, w216, T, d, dff, p_enc, _small_step_splits(T, d, dff),
+                                                       out_drop=(p_enc, seed, stream_ffn_out(l)))
             ga2, gb2n = layernorm_bwd(x1, a2, dn2, T, d, LN_EPS, 0, dx)
             # attention sublayer: x1 = x0 + drop(ctx Wo^T + bo)
-            dyo, gbo = _drop_cast_colsum(dx, T, d, p_enc, seed, stream_attn_out(l))
-            gWo = _weight_grad(dyo, ctxb, T, d, d)
-            dctx = torch.empty((T, d), dtype=_U16, device=dev)
-            gemm(dyo, wo16, T, d, d, b_kmajor=True, Cb=dctx)
-            dqkv = attention_bwd(qkv, ctxb, dctx, lse, st["mask_u8"], B, S, h, dk, p_enc, seed, stream_attn(l))
-            gbqkv = _colsum(dqkv, T, 3 * d)
-            gWqkv = _weight_grad(dqkv, n1, T, 3 * d, d)
-            dn1 = torch.empty((T, d), dtype=torch.float32, device=dev)
-            gemm(dqkv, wqkv, T, d, 3 * d, b_kmajor=True, Cf=dn1)
+            g_attn, (dn1,) = attention_sublayer_bwd(dx, [n1], wqkv, wo16, qkv, ctxb, lse, st["mask_u8"], B, S, h, dk, p_enc, seed, stream_attn(l),
+                                                    (True,), out_drop=(p_enc, seed, stream_attn_out(l)))
             ga1, gb1n = layernorm_bwd(x0, a1, dn1, T, d, LN_EPS, 0, dx)
-            grads[base:base + 16] = [ga1, gb1n, gWqkv[:d], gbqkv[:d], gWqkv[d:2 * d], gbqkv[d:2 * d], gWqkv[2 * d:],
-                                     gbqkv[2 * d:], gWo, gbo, ga2, gb2n, gW1, gb1, gW2, gb2]
+            grads[base:base + 16] = [ga1, gb1n, *g_attn, ga2, gb2n, gW1, gb1, gW2, gb2]
     # ---- FCModel backward
     sizes = [F] + spec.fc_sizes
     for i in reversed(range(len(spec.fc_sizes))):
         n_in, n_out = sizes[i], sizes[i + 1]
-        dy, gb = _drop_cast_colsum(dx, T, n_out, p_fc, seed, stream_fc(i))
-        grads[n_fc0 + 2 * i] = _weight_grad(dy, st["fc_in"][i], T, n_out, n_in)
-        grads[n_fc0 + 2 * i + 1] = gb
-        if i > 0 or spec.input_norm or want_dx:
-            dx = torch.empty((T, n_in), dtype=torch.float32, device=dev)
-            gemm(dy, fc_w16[i], T, n_in, n_out, b_kmajor=True, Cf=dx)
+        want = i > 0 or spec.input_norm or want_dx
+        dx, gW, gb = linear_bwd(dx, st["fc_in"][i], st["fc_w16"][i], T, n_out, n_in, p_fc, seed, stream_fc(i), want)
+        grads[n_fc0 + 2 * i:n_fc0 + 2 * i + 2] = [gW, gb]
     if spec.input_norm:
-        scratch = torch.zeros((T, F), dtype=torch.float32, device=dev)
+        scratch = torch.zeros((T, F), dtype=torch.float32, device=dx.device)
         grads[0], grads[1] = layernorm_bwd(st["xin"], prm[0], dx, T, F, STD_LN_EPS, 1, scratch)
         dx = scratch
     return grads, (dx if want_dx else None)

@@ -37,7 +37,7 @@ def _bf(x):
 
 class _RoundGradBf16(torch.autograd.Function):
     """Identity whose BACKWARD rounds the gradient to bf16: placed where the HIP backward hands a gradient to the next
-    kernel as bf16 (ltr_mi355x/encoder.py _body_backward: dy after the residual-branch dropout, dz1, dctx, dqkv)."""
+    kernel as bf16 (ltr_mi355x/encoder.py ffn_gemm_bwd / attention_sublayer_bwd: dy after the residual-branch dropout, dz1, dctx, dqkv)."""
 
     @staticmethod
     def forward(ctx, x):

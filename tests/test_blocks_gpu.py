@@ -251,3 +251,111 @@ def test_encoder_layer_with_mixed_dropout_probabilities_takes_the_composed_path(
     o2.data.zero_()
     again = torch.autograd.grad(o2.sum(), xg2)[0]
     assert torch.equal(ref, again)
+
+
+class GemmLog:
+    """encoder.gemm, encoder.splitk_epilogue and encoder._drop_cast_colsum wrapped for one call of a stand-alone block (in the spirit of
+    test_encoder_gpu.FfnCalls): what every GEMM was asked for.  The blocks share their launch chains with the fused network
+    (ltr_mi355x.encoder: attention_sublayer_*, ffn_gemm_*); these records pin what the network adds around a sublayer and a block on
+    its own must not get -- residual, output dropout, split-K."""
+
+    def __init__(self, monkeypatch):
+        from ltr_mi355x import encoder as enc
+        self.gemms, self.epilogues, self.grad_drops = [], [], []
+        gemm, epilogue, drop_cast = enc.gemm, enc.splitk_epilogue, enc._drop_cast_colsum
+
+        def logging_gemm(A, B, M, N, K, **kw):
+            self.gemms.append(dict(shape=(M, N, K), a_kmajor=bool(kw.get("a_kmajor")), b_kmajor=bool(kw.get("b_kmajor")),
+                                   drop_p=float(kw.get("drop_p", 0.0)), drop_stream=int(kw.get("drop_stream", 0)),
+                                   residual=kw.get("residual") is not None, bias=kw.get("bias") is not None, splits=int(kw.get("splits", 1)),
+                                   relu=bool(kw.get("relu")), gate=kw.get("gate") is not None, ldc=kw.get("ldc"),
+                                   Cf=kw.get("Cf") is not None, Cb=kw.get("Cb") is not None))
+            return gemm(A, B, M, N, K, **kw)
+
+        def logging_epilogue(*args):
+            self.epilogues.append(args)
+            return epilogue(*args)
+
+        def logging_drop_cast(dx, T, N, p, seed, stream_id):
+            self.grad_drops.append((T, N, float(p)))
+            return drop_cast(dx, T, N, p, seed, stream_id)
+
+        monkeypatch.setattr(enc, "gemm", logging_gemm)
+        monkeypatch.setattr(enc, "splitk_epilogue", logging_epilogue)
+        monkeypatch.setattr(enc, "_drop_cast_colsum", logging_drop_cast)
+
+    def forward_gemms(self, shape):
+        """The row-major x row-major (activation x weight) GEMMs of that (M, N, K)."""
+        return [g for g in self.gemms if g["shape"] == shape and not g["a_kmajor"] and not g["b_kmajor"]]
+
+
+def test_feed_forward_on_its_own_never_splits_k_and_has_no_sublayer_epilogue(monkeypatch):
+    """PositionwiseFeedForward(32, 1024) on 51 tokens: the fused network runs this shape's two (T, d, d_ff) GEMMs as 2 split-K slices
+    with the residual and SublayerConnection's dropout in the reduce; the module on its own is w_2(dropout(relu(w_1 x))) and nothing else
+    (transformer.py:231-237) -- one slice, no split-K epilogue, no residual, no dropout on the output, the module's p on the hidden layer."""
+    from architeture import transformer as T
+    from ltr_mi355x import encoder as enc
+    tokens, d, dff = 51, 32, 1024
+    assert enc._small_step_splits(tokens, d, dff) == 2
+    torch.manual_seed(5)
+    ff = T.PositionwiseFeedForward(d, dff).to(DEV).train()
+    x = torch.randn(3, 17, d, device=DEV, requires_grad=True)
+    log = GemmLog(monkeypatch)
+    ff(x).square().sum().backward()
+    assert x.grad is not None and torch.isfinite(x.grad).all()
+    assert log.epilogues == []
+    (hidden,) = [g for g in log.gemms if g["relu"]]
+    assert hidden["shape"] == (tokens, dff, d) and hidden["bias"] and hidden["Cb"] and not hidden["residual"]
+    assert hidden["drop_p"] == pytest.approx(ff.dropout.p) and ff.dropout.p > 0 and hidden["drop_stream"] == 2
+    (out,) = log.forward_gemms((tokens, d, dff))
+    assert out["splits"] == 1 and out["Cf"] and out["bias"] and not out["residual"] and out["drop_p"] == 0.0
+    (dx,) = [g for g in log.gemms if g["shape"] == (tokens, d, dff) and g["b_kmajor"] and not g["a_kmajor"]]
+    assert dx["splits"] == 1 and dx["Cf"] and not dx["gate"]
+    assert log.grad_drops == [(tokens, d, 0.0)]              # the incoming gradient passes no output dropout
+
+
+def test_multi_head_attention_on_its_own_projects_without_residual_or_output_dropout(monkeypatch):
+    """MultiHeadedAttention(4, 32, 0.1) in train mode: its dropout is the one on the attention probabilities (transformer.py:207);
+    the output projection carries neither a residual nor a dropout (those are SublayerConnection's, which the fused network folds
+    into this GEMM).  query is key is value: ONE (T, 3d, d) projection GEMM; three distinct tensors: three (T, d, d) GEMMs into the
+    column blocks of the packed [T, 3d] tensor (ldc = 3d)."""
+    from architeture import transformer as T
+    torch.manual_seed(6)
+    B_, S, d = 3, 17, 32
+    tokens = B_ * S
+    mha = T.MultiHeadedAttention(4, d, 0.1).to(DEV).train()
+    q, k, v = (torch.randn(B_, S, d, device=DEV, requires_grad=True) for _ in range(3))
+    mask = torch.zeros(B_, 1, S, dtype=torch.bool, device=DEV)
+    mask[1, :, 12:] = True
+    log = GemmLog(monkeypatch)
+    out = mha(q, q, q, mask)
+    assert torch.isfinite(out).all()
+    (qkv,) = log.forward_gemms((tokens, 3 * d, d))
+    assert qkv["Cb"] and qkv["bias"] and qkv["ldc"] in (None, 3 * d)
+    (proj,) = log.forward_gemms((tokens, d, d))
+    assert proj["Cf"] and proj["bias"] and not proj["residual"] and proj["drop_p"] == 0.0
+    assert len(log.gemms) == 2
+    _backward_has_no_output_dropout(log, out, tokens, d)
+    out = mha(q, k, v, mask)
+    assert torch.isfinite(out).all()
+    assert log.forward_gemms((tokens, 3 * d, d)) == []
+    square = log.forward_gemms((tokens, d, d))
+    packed, (proj,) = [g for g in square if g["Cb"]], [g for g in square if g["Cf"]]
+    assert len(packed) == 3 and all(g["ldc"] == 3 * d and g["bias"] for g in packed)
+    assert proj["bias"] and not proj["residual"] and proj["drop_p"] == 0.0
+    assert len(log.gemms) == 4
+    _backward_has_no_output_dropout(log, out, tokens, d)
+    assert all(t.grad is not None and torch.isfinite(t.grad).all() for t in (q, k, v))
+
+
+def _backward_has_no_output_dropout(log, out, tokens, d):
+    """The backward of a stand-alone MultiHeadedAttention: the incoming gradient is cast with p = 0 (no SublayerConnection dropout to
+    undo) and goes through Wo into the bf16 d ctx with a plain GEMM.  Clears the log."""
+    log.gemms.clear()
+    out.square().sum().backward()
+    assert log.grad_drops == [(tokens, d, 0.0)]
+    (dctx,) = [g for g in log.gemms if g["shape"] == (tokens, d, d) and g["b_kmajor"] and not g["a_kmajor"] and g["Cb"]]
+    assert dctx["drop_p"] == 0.0 and not dctx["residual"] and not dctx["gate"] and not dctx["bias"] and dctx["splits"] == 1
+    assert log.epilogues == []
+    log.gemms.clear()
+    log.grad_drops.clear()

@@ -1,5 +1,5 @@
-"""GPU: the GEMM-path FFN the encoder runs below FUSED_FFN_MIN_TOKENS tokens per step (ltr_mi355x.encoder._run_forward /
-_body_backward), against fp64.  The suite forces the fused FFN kernels on (tests/conftest.py); every test here picks its path
+"""GPU: the GEMM-path FFN the encoder runs below FUSED_FFN_MIN_TOKENS tokens per step (ltr_mi355x.encoder.ffn_gemm_fwd /
+ffn_gemm_bwd, as _run_forward / _body_backward call them), against fp64.  The suite forces the fused FFN kernels on (tests/conftest.py); every test here picks its path
 itself with LTR_ENC_FUSED_FFN.
 
   * kernels: the split-K activation GEMMs of that path (forward hid W2^T and input-gradient dz1 W1 layouts) slice by slice and
