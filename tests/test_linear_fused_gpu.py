@@ -352,6 +352,84 @@ def test_precision_gain_over_module_path(dev, S):
     assert e_fused < e_mod and e_fused < 1e-5
 
 
+# ------------------------------------------------------------------------------------------- every loss path in the one-launch step
+def _scale_spread(net, x, sizes, input_norm, target):
+    """Scale the output layer in place so that max |s_k - s_0| over the batch is `target`; returns the fp32 scores after it."""
+    params = net._ltr_params()
+    s = linear_forward(x, [p.detach().cpu().double() for p in params], sizes, input_norm)
+    with torch.no_grad():
+        params[-2].mul_(target / float((s - s[:, :1]).abs().max()))
+    return linear_forward(x, [p.detach().cpu().double() for p in params], sizes, input_norm).to(torch.float32)
+
+
+PATH_REGIMES = {          # regime -> (max |s_k - s_0|, paths of approx_ndcg_slate that must occur in the batch)
+    "noclamp": (6.0, {"noclamp"}), "fast": (30.0, {"fast"}), "perpair": (150.0, {"perpair"}), "mixed": (150.0, {"noclamp", "fast", "perpair"}),
+    "fractional": (6.0, {"fast"}), "front": (30.0, {"fast"}), "input_norm": (30.0, {"fast"}),
+}
+
+
+def _path_batch(regime, S):
+    """(net, x, y, sizes, input_norm) of a regime: 640 documents = 5 tiles of 128, so at grid = 2 a workgroup walks 2 or 3 tiles."""
+    ln = regime == "input_norm"
+    F, sizes = (64, [32, 16]) if ln else (136, SIZES)
+    net = _model("cpu", seed=14, F=F, sizes=sizes, input_norm=ln)
+    B = 640 // S
+    x, y = _data(B, S, F=F, seed=40 + S)
+    g = torch.Generator().manual_seed(S)
+    if ln:
+        x = x * 3.0 + 1.5
+    if regime == "mixed":                             # consecutive slates (and tiles) on different paths; one slate all padding
+        for b in range(B):
+            x[b] *= (0.02, 0.2, 1.0)[b % 3]
+        y[B - 2] = -1.0
+        y[1, S - 5:] = -1.0
+    if regime == "fractional":
+        y = y + 0.25 * torch.rand(B, S, generator=g)
+        y[:, -3:] = -1.0
+    if regime == "front":                             # document 0 padded: its score is the reference point of every exponential
+        y[:, :3] = -1.0
+        y[-1, -4:] = -1.0
+    return net, x, y, sizes, ln
+
+
+@pytest.mark.parametrize("S", [32, 64, 128])
+@pytest.mark.parametrize("regime", list(PATH_REGIMES))
+def test_approxndcg_paths_one_launch(dev, regime, S):
+    """approx_ndcg_slate inside linear_fused_kernel on each of its three paths (tests/slate_loss_cases.path_of names the path of
+    every slate from the fp64 scores), at the default grid and at grid = 2, where a workgroup walks several tiles of different
+    paths and the label histogram has to be clean for each."""
+    import slate_loss_cases as SC
+    from ltr_mi355x.scorer import FusedRanker
+    net, x, y, sizes, ln = _path_batch(regime, S)
+    target, want = PATH_REGIMES[regime]
+    s32 = _scale_spread(net, x, sizes, ln, target)
+    paths = {SC.path_of(s32[b], y[b], 1.0, 1e-10, -1.0) for b in range(x.shape[0])}
+    assert paths >= want and (regime in ("mixed", "perpair") or paths == want), (regime, S, paths)
+    net = net.to(dev)
+    for grid in (None, 2):
+        r = FusedRanker(net, loss="approxNDCG", grid=grid)
+        assert type(r).__name__ == "LinearFusedRanker" and (grid is None or r.grid == 2)
+        _check(net, r, x, y, "approxNDCG", dev, sizes=sizes, input_norm=ln)      # the file's flat 1e-5 on loss and gradients
+
+
+@pytest.mark.parametrize("S", [32, 64, 128])
+@pytest.mark.parametrize("regime", ["wide", "labels30", "input_norm"])
+@pytest.mark.parametrize("apply_sigmoid", [False, True])
+def test_listnet_regimes_one_launch(dev, apply_sigmoid, regime, S):
+    """listnet_slate inside linear_fused_kernel: score spread 60 (every q still above 1e-30), labels up to 30 (softmax(y_true)
+    one-hot to fp32), an input-norm network; default grid and grid = 2."""
+    from ltr_mi355x.scorer import FusedRanker
+    net, x, y, sizes, ln = _path_batch("input_norm" if regime == "input_norm" else "fast", S)
+    if regime == "labels30":
+        y = torch.randint(0, 31, y.shape, generator=torch.Generator().manual_seed(S)).float()
+    s32 = _scale_spread(net, x, sizes, ln, 30.0 if regime != "labels30" else 4.0)
+    assert float(torch.softmax(s32, dim=1).min()) >= 1e-30
+    net = net.to(dev)
+    for grid in (None, 2):
+        r = FusedRanker(net, loss="listnet", apply_sigmoid=apply_sigmoid, grid=grid)
+        _check(net, r, x, y, "listnet", dev, sizes=sizes, input_norm=ln, apply_sigmoid=apply_sigmoid)
+
+
 # ---------------------------------------------------------------------------------------------------------- data parallel
 def _free_port():
     with socket.socket() as s:
