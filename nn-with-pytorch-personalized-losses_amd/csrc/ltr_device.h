@@ -33,6 +33,20 @@ __device__ __forceinline__ long long ltr_wave_uniform(long long v) {
 
 namespace ltr {
 
+// What a launcher returns after its launch: 0 (LTR_OK) or HIP's error code, which is positive.
+inline int launch_status() {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+// More than 64 KB of dynamic LDS needs the kernel's opt-in (up to the 160 KB of a gfx950 CU); below that nothing is called.
+template <class K>
+inline int allow_lds(K kernel, size_t lds) {
+    if (lds <= 64 * 1024) return 0;
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return e == hipSuccess ? 0 : (int)e;
+}
+
 // 1 / x on the hardware reciprocal (v_rcp_f32, 1 ulp).  NOT __frcp_rn: without fast-math hipcc expands that to the correctly
 // rounded IEEE division sequence (v_div_scale, v_rcp, four fma, v_div_fmas, v_div_fixup: an 11-instruction dependent chain) --
 // which is what sat in the inner loop of every pair sweep until round 3 (profiles/r03_variant_ab.json).

@@ -37,11 +37,6 @@ constexpr int kLinFusedMaxF = 256;      // one-launch path (the 128-document X t
 constexpr int kTile = 128;              // documents per super-tile of the one-launch kernel
 constexpr float kLnEps = 1e-5f;         // nn.LayerNorm default (multiLayer.py:28)
 
-inline int launch_status() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LTR_OK : (int)e;
-}
-
 // The network by value: widths, parameter pointers (LTRModel._ltr_params() order), flat-gradient and workspace offsets.
 struct LinNet {
     int L, F, ln;
@@ -721,17 +716,10 @@ __global__ void __launch_bounds__(256) linear_risk_combine_kernel(const float *_
     }
 }
 
-template <class K>
-int set_lds(K kernel, size_t lds) {
-    if (lds <= 64 * 1024) return LTR_OK;
-    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return e == hipSuccess ? LTR_OK : (int)e;
-}
-
 template <int LK, int SCH, bool LN>
 int launch_fused(const FusedArgs &a, int grid, hipStream_t stream) {
     const size_t lds = fused_lds_bytes(a.F, a.S);
-    if (int rc = set_lds(linear_fused_kernel<LK, SCH, LN>, lds)) return rc;
+    if (int rc = allow_lds(linear_fused_kernel<LK, SCH, LN>, lds)) return rc;
     hipLaunchKernelGGL((linear_fused_kernel<LK, SCH, LN>), dim3(grid), dim3(256), lds, stream, a);
     return launch_status();
 }
@@ -893,10 +881,10 @@ int ltr_linear_risk_rows(const float *X, const float *labels, int B, int S, int 
     const size_t lds = risk_rows_lds_bytes(F);
     hipStream_t s = (hipStream_t)stream;
     if (input_norm) {
-        if (int rc = set_lds(linear_risk_rows_kernel<true>, lds)) return rc;
+        if (int rc = allow_lds(linear_risk_rows_kernel<true>, lds)) return rc;
         hipLaunchKernelGGL(linear_risk_rows_kernel<true>, ltr_grid(grid), dim3(256), lds, s, a);
     } else {
-        if (int rc = set_lds(linear_risk_rows_kernel<false>, lds)) return rc;
+        if (int rc = allow_lds(linear_risk_rows_kernel<false>, lds)) return rc;
         hipLaunchKernelGGL(linear_risk_rows_kernel<false>, ltr_grid(grid), dim3(256), lds, s, a);
     }
     return launch_status();

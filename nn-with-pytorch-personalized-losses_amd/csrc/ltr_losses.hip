@@ -6,55 +6,11 @@
 // (S^2 sigmoids per slate against 12*S bytes of HBM traffic), see DESIGN.md.
 #include "../../include/ltr_mi355x.h"
 #include "ltr_slate_losses.h"
+#include <type_traits>
 
 using namespace ltr;
 
 namespace {
-
-inline int check_slates(const void *a, const void *b, const void *c, int B, int S) {
-    if (!a || !b || !c) return LTR_ERR_NULL;
-    if (B < 0 || S < 1 || S > LTR_MAX_SLATE) return LTR_ERR_SHAPE;
-    return LTR_OK;
-}
-
-inline int launch_status() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LTR_OK : (int)e;
-}
-
-struct SlateLaunch {
-    int group, block, gpb, grid;
-    size_t lds;
-};
-
-// arrays_per_slate: number of [S] float arrays each slate group keeps in LDS.
-inline SlateLaunch plan(int B, int S, int arrays_per_slate) {
-    SlateLaunch L;
-    L.group = pick_group(S);
-    L.block = L.group < 256 ? 256 : L.group;
-    L.gpb = L.block / L.group;
-    L.grid = (B + L.gpb - 1) / L.gpb;
-    const int s_al = (S + 3) & ~3;
-    L.lds = (size_t)L.gpb * (arrays_per_slate * s_al + L.group + 32) * sizeof(float);
-    return L;
-}
-
-// Threads per slate of the one-slate-per-workgroup pair kernels: at least 256, but never more than one wave of column groups
-// per row -- row_reduce combines the CG replicas of a row inside ONE wave (CG <= 64), and 256 threads on S <= 2 documents
-// would make CG 128 / 256 (doubled rank counts at S = 2).  64 threads at S = 1, 128 at S = 2, unchanged from S = 3 on.
-inline int pair_group(int S) {
-    int g = pick_group(S) < 256 ? 256 : pick_group(S);
-    const int np2 = next_pow2(S);
-    while (g / (np2 < g ? np2 : g) > LTR_WAVE) g >>= 1;
-    return g;
-}
-
-template <class K>
-inline int allow_lds(K kernel, size_t lds) {
-    if (lds <= 64 * 1024) return LTR_OK;
-    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return e == hipSuccess ? LTR_OK : (int)e;
-}
 
 // ------------------------------------------------------------------------------------ approxNDCG
 constexpr int kApproxArrays = 7;  // sc yl gn gg uu mk um
@@ -904,9 +860,9 @@ lambda_blocked_ragged_kernel(const float *__restrict__ scores, const float *__re
 // ---- The Lambda-type risk losses on a ragged tier: the three kernels above with the slate taken from the
 // tier's query list.  ONE slate owns its workgroup, so an idle or misfit slot leaves as a whole block before the first barrier and
 // every barrier inside the slate functions is reached by all threads of the block (section 4.9's rule; no mixed-barrier site here).
-// The group size comes from the tier's s_max by the rectangular launcher's formula -- constant inside a tier, which depends on the
-// length through next_pow2 only -- so with all lengths equal these are the rectangular launches' bits.  n_docs = the documents of
-// the whole batch: system k's column sums start at colsum[k * n_docs].
+// The group size comes from the tier's s_max by the geometry function the rectangular launcher calls -- constant inside a tier, which
+// depends on the length through next_pow2 only -- so with all lengths equal these are the rectangular launches' bits.  n_docs = the
+// documents of the whole batch: system k's column sums start at colsum[k * n_docs].
 template <int SCH>
 __global__ void __launch_bounds__(1024)
 lambda_colsum_sys_ragged_kernel(const float *__restrict__ y_pred, const float *__restrict__ y_true, const float *__restrict__ y_base,
@@ -953,6 +909,13 @@ lambda_colsum_sys_bwd_ragged_kernel(const float *__restrict__ y_pred, const floa
     colsum_sys_bwd_slate<SCH>(y_pred, y_true, rq.off, rq.S, group, P, pad, jac, coef[rq.q * coef_stride], dy_pred, smem);
 }
 
+// ------------------------------------------------------------------------------------------------ the launch layer
+inline int check_slates(const void *a, const void *b, const void *c, int B, int S) {
+    if (!a || !b || !c) return LTR_ERR_NULL;
+    if (B < 0 || S < 1 || S > LTR_MAX_SLATE) return LTR_ERR_SHAPE;
+    return LTR_OK;
+}
+
 inline int check_ragged(const void *a, const void *b, const void *c, const void *offsets, int n_queries, int s_max) {
     if (!a || !b || !c || !offsets) return LTR_ERR_NULL;
     if (n_queries < 0 || s_max < 1 || s_max > LTR_MAX_SLATE) return LTR_ERR_SHAPE;
@@ -973,17 +936,91 @@ inline int make_lambda_params(int scheme, int k, float sigma, float mu, float ep
     return LTR_OK;
 }
 
-#define LTR_DISPATCH_SCHEME(scheme, CALL)          \
-    switch (scheme) {                              \
-        case 0: { CALL(0); break; }                \
-        case 1: { CALL(1); break; }                \
-        case 2: { CALL(2); break; }                \
-        case 3: { CALL(3); break; }                \
-        case 4: { CALL(4); break; }                \
-        case 5: { CALL(5); break; }                \
-        case 6: { CALL(6); break; }                \
-        default: { CALL(7); break; }               \
+// Geometry.  One function per kernel family, of the slate length alone: a rectangular launcher passes S, a ragged one its tier's
+// s_max, and nothing else computes a group size, a block or an LDS size -- which is what makes a ragged launch of equal lengths the
+// rectangular launch (the tier rule).
+
+// Slates that share a workgroup of at least 256 threads: `group` threads and `arrays` [S] float arrays in LDS per slate.
+struct SlateLaunch {
+    int group, block, gpb;
+    size_t lds;
+    int grid(int n_slates) const { return (n_slates + gpb - 1) / gpb; }
+};
+
+inline SlateLaunch shared_plan(int group, int S, int arrays) {
+    SlateLaunch L;
+    L.group = group;
+    L.block = group < 256 ? 256 : group;
+    L.gpb = L.block / group;
+    L.lds = (size_t)L.gpb * (arrays * ((S + 3) & ~3) + group + 32) * sizeof(float);
+    return L;
+}
+
+// One thread per document: ListNet's O(S) work per slate, and the column-sum forward kernels (a thread owns a column).
+inline int doc_group(int S) { return next_pow2(S) < 64 ? 64 : (next_pow2(S) > 1024 ? 1024 : next_pow2(S)); }
+
+// The document-order pair kernels (approxNDCG, lambda_kernel): pick_group's two threads per row.
+inline SlateLaunch plan(int S, int arrays) { return shared_plan(pick_group(S), S, arrays); }
+inline SlateLaunch listnet_plan(int S) { return shared_plan(doc_group(S), S, 2); }
+
+// Threads per slate of the one-slate-per-workgroup pair kernels: at least 256, but never more than one wave of column groups
+// per row -- row_reduce combines the CG replicas of a row inside ONE wave (CG <= 64), and 256 threads on S <= 2 documents
+// would make CG 128 / 256 (doubled rank counts at S = 2).  64 threads at S = 1, 128 at S = 2, unchanged from S = 3 on.
+inline int pair_group(int S) {
+    int g = pick_group(S) < 256 ? 256 : pick_group(S);
+    const int np2 = next_pow2(S);
+    while (g / (np2 < g ? np2 : g) > LTR_WAVE) g >>= 1;
+    return g;
+}
+
+// LDS of a one-slate-per-workgroup Lambda kernel: lambda_carve's arrays, `extra` more [S] arrays, make_group's scratch.
+inline size_t pair_lds(int extra, int S, int group) {
+    return (size_t)((kLambdaArrays + extra) * ((S + 3) & ~3) + group + 32) * sizeof(float);
+}
+
+// lambdaLoss: the rank-space sweep (lambda_blocked_kernel) for 256 <= S <= 1024 and every scheme but ndcgLoss1 -- one slate per
+// workgroup, one wave per 64 ranks, LambdaRankLds next to lambda_carve's arrays -- and lambda_kernel on plan() everywhere else.
+struct LambdaLaunch : SlateLaunch {
+    bool blocked;
+};
+
+inline LambdaLaunch lambda_plan(int S, int scheme) {
+    LambdaLaunch L;
+    L.blocked = S >= 256 && S <= 1024 && scheme != LTR_SCHEME_NDCG_LOSS1;
+    if (!L.blocked) {
+        static_cast<SlateLaunch &>(L) = plan(S, kLambdaArrays);
+        return L;
     }
+    const int s64 = (S + 63) & ~63;
+    L.group = L.block = s64;
+    L.gpb = 1;
+    L.lds = (size_t)(kLambdaArrays * ((S + 3) & ~3) + 5 * s64 + s64 + 32) * sizeof(float);
+    return L;
+}
+
+// Every launch of this file: the LDS opt-in above 64 KB, `blocks` workgroups through ltr_grid, the launch's status.
+template <class... KA, class... A>
+inline int launch(void (*kernel)(KA...), long long blocks, int block, size_t lds, void *stream, A... args) {
+    if (int rc = allow_lds(kernel, lds)) return rc;
+    hipLaunchKernelGGL(kernel, ltr_grid(blocks), dim3(block), lds, (hipStream_t)stream, static_cast<KA>(args)...);
+    return launch_status();
+}
+
+// The Lambda kernels are templates on the weighting scheme: f(std::integral_constant<int, SCH>()) for a scheme that
+// make_lambda_params has accepted (0 .. 7).
+template <class F>
+inline int with_scheme(int scheme, F f) {
+    switch (scheme) {
+        case 0: return f(std::integral_constant<int, 0>());
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 5: return f(std::integral_constant<int, 5>());
+        case 6: return f(std::integral_constant<int, 6>());
+        default: return f(std::integral_constant<int, 7>());
+    }
+}
 
 }  // namespace
 
@@ -1007,35 +1044,25 @@ const char *ltr_error_string(int code) {
 int ltr_reduce_sum_f32(const float *in, int64_t n, float scale, float *out, void *stream) {
     if (!in || !out) return LTR_ERR_NULL;
     if (n < 0) return LTR_ERR_SHAPE;
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, in, n, scale, out);
-    return launch_status();
+    return launch(reduce_sum_kernel, 1, 1024, 0, stream, in, n, scale, out);
 }
 
 int ltr_approxndcg_fwd_bwd(const float *scores, const float *labels, int B, int S, float alpha, float eps,
                            float pad, float grad_scale, float *slate_loss, float *dscores, void *stream) {
     if (int rc = check_slates(scores, labels, slate_loss, B, S)) return rc;
     if (B == 0) return LTR_OK;
-    const SlateLaunch L = plan(B, S, kApproxArrays);
-    if (int rc = allow_lds(approxndcg_kernel, L.lds)) return rc;
-    hipLaunchKernelGGL(approxndcg_kernel, ltr_grid(L.grid), dim3(L.block), L.lds, (hipStream_t)stream, scores, labels,
-                       B, S, L.group, alpha, eps, pad, grad_scale, slate_loss, dscores);
-    return launch_status();
+    const SlateLaunch L = plan(S, kApproxArrays);
+    return launch(approxndcg_kernel, L.grid(B), L.block, L.lds, stream, scores, labels, B, S, L.group, alpha, eps, pad, grad_scale,
+                  slate_loss, dscores);
 }
 
 int ltr_listnet_fwd_bwd(const float *y_true, const float *y_pred, int B, int S, int apply_sigmoid,
                         float grad_scale, float *slate_loss, float *dscores, void *stream) {
     if (int rc = check_slates(y_true, y_pred, slate_loss, B, S)) return rc;
     if (B == 0) return LTR_OK;
-    SlateLaunch L = plan(B, S, 2);
-    // O(S) work per slate: one thread per document is plenty.
-    L.group = next_pow2(S) < 64 ? 64 : (next_pow2(S) > 1024 ? 1024 : next_pow2(S));
-    L.block = L.group < 256 ? 256 : L.group;
-    L.gpb = L.block / L.group;
-    L.grid = (B + L.gpb - 1) / L.gpb;
-    L.lds = (size_t)L.gpb * (2 * ((S + 3) & ~3) + L.group + 32) * sizeof(float);
-    hipLaunchKernelGGL(listnet_kernel, ltr_grid(L.grid), dim3(L.block), L.lds, (hipStream_t)stream, y_true, y_pred, B,
-                       S, L.group, apply_sigmoid, grad_scale, slate_loss, dscores);
-    return launch_status();
+    const SlateLaunch L = listnet_plan(S);
+    return launch(listnet_kernel, L.grid(B), L.block, L.lds, stream, y_true, y_pred, B, S, L.group, apply_sigmoid, grad_scale,
+                  slate_loss, dscores);
 }
 
 int ltr_lambda_fwd_bwd(const float *scores, const float *labels, int B, int S, int scheme, int k, float sigma,
@@ -1046,33 +1073,16 @@ int ltr_lambda_fwd_bwd(const float *scores, const float *labels, int B, int S, i
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
-    if (S >= 256 && S <= 1024 && scheme != LTR_SCHEME_NDCG_LOSS1) {
-        const int s_al = (S + 3) & ~3, s64 = (S + 63) & ~63;
-        const size_t lds = (size_t)(kLambdaArrays * s_al + 5 * s64 + s64 + 32) * sizeof(float);
-#define CALLB(SCH)                                                                                                \
-    if (int rc = allow_lds(lambda_blocked_kernel<SCH>, lds)) return rc;                                           \
-    hipLaunchKernelGGL(lambda_blocked_kernel<SCH>, ltr_grid(B), dim3(s64), lds, (hipStream_t)stream, scores, labels,  \
-                       B, S, P, pad, grad_scale, slate_loss, slate_count, dscores)
-        switch (scheme) {
-            case 0: { CALLB(0); break; }
-            case 2: { CALLB(2); break; }
-            case 3: { CALLB(3); break; }
-            case 4: { CALLB(4); break; }
-            case 5: { CALLB(5); break; }
-            case 6: { CALLB(6); break; }
-            default: { CALLB(7); break; }
-        }
-#undef CALLB
-        return launch_status();
-    }
-    const SlateLaunch L = plan(B, S, kLambdaArrays);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_kernel<SCH>, L.lds)) return rc;                                                 \
-    hipLaunchKernelGGL(lambda_kernel<SCH>, ltr_grid(L.grid), dim3(L.block), L.lds, (hipStream_t)stream, scores,       \
-                       labels, B, S, L.group, P, pad, grad_scale, slate_loss, slate_count, dscores)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    const LambdaLaunch L = lambda_plan(S, scheme);
+    return with_scheme(scheme, [&](auto sch) {
+        constexpr int SCH = decltype(sch)::value;
+        if constexpr (SCH != LTR_SCHEME_NDCG_LOSS1)      // the rank-space sweep is not built for ndcgLoss1: lambda_plan never picks it
+            if (L.blocked)
+                return launch(lambda_blocked_kernel<SCH>, L.grid(B), L.block, L.lds, stream, scores, labels, B, S, P, pad, grad_scale,
+                              slate_loss, slate_count, dscores);
+        return launch(lambda_kernel<SCH>, L.grid(B), L.block, L.lds, stream, scores, labels, B, S, L.group, P, pad, grad_scale,
+                      slate_loss, slate_count, dscores);
+    });
 }
 
 int ltr_lambda_pairs_fwd(const float *scores, const float *labels, int B, int S, int scheme, int k, float sigma,
@@ -1083,14 +1093,10 @@ int ltr_lambda_pairs_fwd(const float *scores, const float *labels, int B, int S,
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
     const int group = pair_group(S);
-    const size_t lds = (size_t)((kLambdaArrays + 1) * ((S + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_pairs_fwd_kernel<SCH>, lds)) return rc;                                         \
-    hipLaunchKernelGGL(lambda_pairs_fwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, scores,      \
-                       labels, B, S, group, P, pad, losses, keep, rank)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_pairs_fwd_kernel<decltype(sch)::value>, B, group, pair_lds(1, S, group), stream, scores, labels, B, S,
+                      group, P, pad, losses, keep, rank);
+    });
 }
 
 int ltr_lambda_pairs_bwd(const float *scores, const float *labels, int B, int S, int scheme, int k, float sigma,
@@ -1102,14 +1108,10 @@ int ltr_lambda_pairs_bwd(const float *scores, const float *labels, int B, int S,
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
     const int group = pair_group(S);
-    const size_t lds = (size_t)(kLambdaArrays * ((S + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_pairs_bwd_kernel<SCH>, lds)) return rc;                                         \
-    hipLaunchKernelGGL(lambda_pairs_bwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, scores,      \
-                       labels, B, S, group, P, pad, grad_losses, 0, dscores)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_pairs_bwd_kernel<decltype(sch)::value>, B, group, pair_lds(0, S, group), stream, scores, labels, B, S,
+                      group, P, pad, grad_losses, 0, dscores);
+    });
 }
 
 int ltr_lambda_colsum_fwd(const float *scores, const float *labels, int B, int S, int scheme, int k, float sigma,
@@ -1118,15 +1120,11 @@ int ltr_lambda_colsum_fwd(const float *scores, const float *labels, int B, int S
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
-    const int group = next_pow2(S) < 64 ? 64 : (next_pow2(S) > 1024 ? 1024 : next_pow2(S));
-    const size_t lds = (size_t)((kLambdaArrays + 1) * ((S + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_colsum_fwd_kernel<SCH>, lds)) return rc;                                        \
-    hipLaunchKernelGGL(lambda_colsum_fwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, scores,     \
-                       labels, B, S, group, P, pad, colsum)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    const int group = doc_group(S);
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_colsum_fwd_kernel<decltype(sch)::value>, B, group, pair_lds(1, S, group), stream, scores, labels, B, S,
+                      group, P, pad, colsum);
+    });
 }
 
 int ltr_lambda_colsum_bwd(const float *scores, const float *labels, int B, int S, int scheme, int k, float sigma,
@@ -1138,14 +1136,10 @@ int ltr_lambda_colsum_bwd(const float *scores, const float *labels, int B, int S
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
     const int group = pair_group(S);
-    const size_t lds = (size_t)(kLambdaArrays * ((S + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_pairs_bwd_kernel<SCH>, lds)) return rc;                                         \
-    hipLaunchKernelGGL(lambda_pairs_bwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, scores,      \
-                       labels, B, S, group, P, pad, grad_colsum, 1, dscores)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_pairs_bwd_kernel<decltype(sch)::value>, B, group, pair_lds(0, S, group), stream, scores, labels, B, S,
+                      group, P, pad, grad_colsum, 1, dscores);
+    });
 }
 
 int ltr_lambda_colsum_sys_fwd(const float *y_pred, const float *y_true, const float *y_base, int B, int S, int n_base, int scheme,
@@ -1155,15 +1149,11 @@ int ltr_lambda_colsum_sys_fwd(const float *y_pred, const float *y_true, const fl
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
-    const int group = next_pow2(S) < 64 ? 64 : (next_pow2(S) > 1024 ? 1024 : next_pow2(S));
-    const size_t lds = (size_t)((kLambdaArrays + 1) * ((S + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_colsum_sys_fwd_kernel<SCH>, lds)) return rc;                                    \
-    hipLaunchKernelGGL(lambda_colsum_sys_fwd_kernel<SCH>, ltr_grid((long long)(n_base + 2) * B), dim3(group), lds, (hipStream_t)stream,   \
-                       y_pred, y_true, y_base, B, S, n_base, group, P, pad, colsum)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    const int group = doc_group(S);
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_colsum_sys_fwd_kernel<decltype(sch)::value>, (long long)(n_base + 2) * B, group, pair_lds(1, S, group),
+                      stream, y_pred, y_true, y_base, B, S, n_base, group, P, pad, colsum);
+    });
 }
 
 int ltr_lambda_colsum_sys_bwd(const float *y_pred, const float *y_true, int B, int S, int scheme, int k, float sigma, float mu,
@@ -1174,14 +1164,10 @@ int ltr_lambda_colsum_sys_bwd(const float *y_pred, const float *y_true, int B, i
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
     const int group = pair_group(S);
-    const size_t lds = (size_t)((kLambdaArrays + 1) * ((S + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_colsum_sys_bwd_kernel<SCH>, lds)) return rc;                                    \
-    hipLaunchKernelGGL(lambda_colsum_sys_bwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, y_pred, y_true, B, S, \
-                       group, P, pad, grad_colsum, nullptr, 0, dy_pred)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_colsum_sys_bwd_kernel<decltype(sch)::value>, B, group, pair_lds(1, S, group), stream, y_pred, y_true, B,
+                      S, group, P, pad, grad_colsum, nullptr, 0, dy_pred);
+    });
 }
 
 int ltr_lambda_risk_model_fwd(const float *y_pred, const float *y_true, const float *cache, int cache_stride, int n_cached, int B, int S,
@@ -1194,15 +1180,11 @@ int ltr_lambda_risk_model_fwd(const float *y_pred, const float *y_true, const fl
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
-    const int group = next_pow2(S) < 64 ? 64 : (next_pow2(S) > 1024 ? 1024 : next_pow2(S));     // = ltr_lambda_colsum_sys_fwd's
-    const size_t lds = (size_t)((kLambdaArrays + 2) * ((S + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_risk_model_fwd_kernel<SCH>, lds)) return rc;                                    \
-    hipLaunchKernelGGL(lambda_risk_model_fwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, y_pred, y_true, cache, \
-                       cache_stride, n_cached, B, S, group, P, pad, lt, mat, jac)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    const int group = doc_group(S);
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_risk_model_fwd_kernel<decltype(sch)::value>, B, group, pair_lds(2, S, group), stream, y_pred, y_true,
+                      cache, cache_stride, n_cached, B, S, group, P, pad, lt, mat, jac);
+    });
 }
 
 int ltr_lambda_colsum_sys_bwd_coef(const float *y_pred, const float *y_true, int B, int S, int scheme, int k, float sigma, float mu,
@@ -1215,14 +1197,10 @@ int ltr_lambda_colsum_sys_bwd_coef(const float *y_pred, const float *y_true, int
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (B == 0) return LTR_OK;
     const int group = pair_group(S);
-    const size_t lds = (size_t)((kLambdaArrays + 1) * ((S + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_colsum_sys_bwd_kernel<SCH>, lds)) return rc;                                    \
-    hipLaunchKernelGGL(lambda_colsum_sys_bwd_kernel<SCH>, ltr_grid(B), dim3(group), lds, (hipStream_t)stream, y_pred, y_true, B, S, \
-                       group, P, pad, jac, coef, coef_stride, dy_pred)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_colsum_sys_bwd_kernel<decltype(sch)::value>, B, group, pair_lds(1, S, group), stream, y_pred, y_true, B,
+                      S, group, P, pad, jac, coef, coef_stride, dy_pred);
+    });
 }
 
 int ltr_approxndcg_ragged_fwd_bwd(const float *scores, const float *labels, const int64_t *offsets, const int32_t *queries,
@@ -1230,11 +1208,9 @@ int ltr_approxndcg_ragged_fwd_bwd(const float *scores, const float *labels, cons
                                   float *dscores, void *stream) {
     if (int rc = check_ragged(scores, labels, slate_loss, offsets, n_queries, s_max)) return rc;
     if (n_queries == 0) return LTR_OK;
-    const SlateLaunch L = plan(n_queries, s_max, kApproxArrays);
-    if (int rc = allow_lds(approxndcg_ragged_kernel, L.lds)) return rc;
-    hipLaunchKernelGGL(approxndcg_ragged_kernel, ltr_grid(L.grid), dim3(L.block), L.lds, (hipStream_t)stream, scores, labels,
-                       offsets, queries, n_queries, s_max, L.group, alpha, eps, pad, grad_scale, slate_loss, dscores);
-    return launch_status();
+    const SlateLaunch L = plan(s_max, kApproxArrays);
+    return launch(approxndcg_ragged_kernel, L.grid(n_queries), L.block, L.lds, stream, scores, labels, offsets, queries, n_queries,
+                  s_max, L.group, alpha, eps, pad, grad_scale, slate_loss, dscores);
 }
 
 int ltr_listnet_ragged_fwd_bwd(const float *y_true, const float *y_pred, const int64_t *offsets, const int32_t *queries,
@@ -1242,13 +1218,9 @@ int ltr_listnet_ragged_fwd_bwd(const float *y_true, const float *y_pred, const i
                                void *stream) {
     if (int rc = check_ragged(y_true, y_pred, slate_loss, offsets, n_queries, s_max)) return rc;
     if (n_queries == 0) return LTR_OK;
-    // ltr_listnet_fwd_bwd's geometry: one thread per document
-    const int group = next_pow2(s_max) < 64 ? 64 : (next_pow2(s_max) > 1024 ? 1024 : next_pow2(s_max));
-    const int block = group < 256 ? 256 : group, gpb = block / group;
-    const size_t lds = (size_t)gpb * (2 * ((s_max + 3) & ~3) + group + 32) * sizeof(float);
-    hipLaunchKernelGGL(listnet_ragged_kernel, ltr_grid((n_queries + gpb - 1) / gpb), dim3(block), lds, (hipStream_t)stream, y_true,
-                       y_pred, offsets, queries, n_queries, s_max, group, apply_sigmoid, grad_scale, slate_loss, dscores);
-    return launch_status();
+    const SlateLaunch L = listnet_plan(s_max);
+    return launch(listnet_ragged_kernel, L.grid(n_queries), L.block, L.lds, stream, y_true, y_pred, offsets, queries, n_queries,
+                  s_max, L.group, apply_sigmoid, grad_scale, slate_loss, dscores);
 }
 
 int ltr_lambda_ragged_fwd_bwd(const float *scores, const float *labels, const int64_t *offsets, const int32_t *queries,
@@ -1260,37 +1232,17 @@ int ltr_lambda_ragged_fwd_bwd(const float *scores, const float *labels, const in
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (n_queries == 0) return LTR_OK;
-    if (s_max >= 256 && s_max <= 1024 && scheme != LTR_SCHEME_NDCG_LOSS1) {       // ltr_lambda_fwd_bwd's dispatch, on the tier's s_max
-        const int s_al = (s_max + 3) & ~3, s64 = (s_max + 63) & ~63;
-        const size_t lds = (size_t)(kLambdaArrays * s_al + 5 * s64 + s64 + 32) * sizeof(float);
-#define CALLB(SCH)                                                                                                \
-    if (int rc = allow_lds(lambda_blocked_ragged_kernel<SCH>, lds)) return rc;                                    \
-    hipLaunchKernelGGL(lambda_blocked_ragged_kernel<SCH>, ltr_grid(n_queries), dim3(s64), lds, (hipStream_t)stream, scores, \
-                       labels, offsets, queries, n_queries, s_max, P, pad, grad_scale, slate_loss, slate_count, dscores)
-        switch (scheme) {
-            case 0: { CALLB(0); break; }
-            case 2: { CALLB(2); break; }
-            case 3: { CALLB(3); break; }
-            case 4: { CALLB(4); break; }
-            case 5: { CALLB(5); break; }
-            case 6: { CALLB(6); break; }
-            default: { CALLB(7); break; }
-        }
-#undef CALLB
-        return launch_status();
-    }
-    const SlateLaunch L = plan(n_queries, s_max, kLambdaArrays);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_ragged_kernel<SCH>, L.lds)) return rc;                                          \
-    hipLaunchKernelGGL(lambda_ragged_kernel<SCH>, ltr_grid(L.grid), dim3(L.block), L.lds, (hipStream_t)stream, scores, labels, \
-                       offsets, queries, n_queries, s_max, L.group, P, pad, grad_scale, slate_loss, slate_count, dscores)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    const LambdaLaunch L = lambda_plan(s_max, scheme);
+    return with_scheme(scheme, [&](auto sch) {
+        constexpr int SCH = decltype(sch)::value;
+        if constexpr (SCH != LTR_SCHEME_NDCG_LOSS1)
+            if (L.blocked)
+                return launch(lambda_blocked_ragged_kernel<SCH>, L.grid(n_queries), L.block, L.lds, stream, scores, labels, offsets,
+                              queries, n_queries, s_max, P, pad, grad_scale, slate_loss, slate_count, dscores);
+        return launch(lambda_ragged_kernel<SCH>, L.grid(n_queries), L.block, L.lds, stream, scores, labels, offsets, queries,
+                      n_queries, s_max, L.group, P, pad, grad_scale, slate_loss, slate_count, dscores);
+    });
 }
-
-// group sizes of the rectangular launchers, on the tier's s_max
-static inline int colsum_fwd_group(int S) { return next_pow2(S) < 64 ? 64 : (next_pow2(S) > 1024 ? 1024 : next_pow2(S)); }
 
 int ltr_lambda_colsum_sys_ragged_fwd(const float *y_pred, const float *y_true, const float *y_base, const int64_t *offsets,
                                      const int32_t *queries, int n_queries, int s_max, int64_t n_docs, int n_base, int scheme, int k,
@@ -1301,16 +1253,12 @@ int ltr_lambda_colsum_sys_ragged_fwd(const float *y_pred, const float *y_true, c
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (n_queries == 0) return LTR_OK;
-    const int group = colsum_fwd_group(s_max);
-    const size_t lds = (size_t)((kLambdaArrays + 1) * ((s_max + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_colsum_sys_ragged_kernel<SCH>, lds)) return rc;                                 \
-    hipLaunchKernelGGL(lambda_colsum_sys_ragged_kernel<SCH>, ltr_grid((long long)(n_base + 2) * n_queries), dim3(group), lds,       \
-                       (hipStream_t)stream, y_pred, y_true, y_base, offsets, queries, n_queries, s_max, (long long)n_docs, n_base,   \
-                       group, P, pad, colsum)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    const int group = doc_group(s_max);
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_colsum_sys_ragged_kernel<decltype(sch)::value>, (long long)(n_base + 2) * n_queries, group,
+                      pair_lds(1, s_max, group), stream, y_pred, y_true, y_base, offsets, queries, n_queries, s_max, n_docs, n_base,
+                      group, P, pad, colsum);
+    });
 }
 
 int ltr_lambda_risk_model_ragged_fwd(const float *y_pred, const float *y_true, const float *cache, int cache_stride,
@@ -1324,16 +1272,12 @@ int ltr_lambda_risk_model_ragged_fwd(const float *y_pred, const float *y_true, c
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (n_queries == 0) return LTR_OK;
-    const int group = colsum_fwd_group(s_max);                     // = ltr_lambda_risk_model_fwd's
-    const size_t lds = (size_t)((kLambdaArrays + 2) * ((s_max + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_risk_model_ragged_kernel<SCH>, lds)) return rc;                                 \
-    hipLaunchKernelGGL(lambda_risk_model_ragged_kernel<SCH>, ltr_grid(n_queries), dim3(group), lds, (hipStream_t)stream, y_pred, y_true, \
-                       cache, cache_stride, ideal_colsum, n_cached, offsets, queries, n_queries, s_max, (long long)n_docs, group, P, pad, \
-                       lt, mat, jac)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    const int group = doc_group(s_max);
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_risk_model_ragged_kernel<decltype(sch)::value>, n_queries, group, pair_lds(2, s_max, group), stream,
+                      y_pred, y_true, cache, cache_stride, ideal_colsum, n_cached, offsets, queries, n_queries, s_max, n_docs, group, P,
+                      pad, lt, mat, jac);
+    });
 }
 
 int ltr_lambda_colsum_sys_ragged_bwd_coef(const float *y_pred, const float *y_true, const int64_t *offsets, const int32_t *queries,
@@ -1346,15 +1290,11 @@ int ltr_lambda_colsum_sys_ragged_bwd_coef(const float *y_pred, const float *y_tr
     LambdaParams P;
     if (int rc = make_lambda_params(scheme, k, sigma, mu, eps, log_base, &P)) return rc;
     if (n_queries == 0) return LTR_OK;
-    const int group = pair_group(s_max);                           // = ltr_lambda_colsum_sys_bwd_coef's
-    const size_t lds = (size_t)((kLambdaArrays + 1) * ((s_max + 3) & ~3) + group + 32) * sizeof(float);
-#define CALL(SCH)                                                                                                 \
-    if (int rc = allow_lds(lambda_colsum_sys_bwd_ragged_kernel<SCH>, lds)) return rc;                             \
-    hipLaunchKernelGGL(lambda_colsum_sys_bwd_ragged_kernel<SCH>, ltr_grid(n_queries), dim3(group), lds, (hipStream_t)stream, y_pred,  \
-                       y_true, offsets, queries, n_queries, s_max, (long long)n_docs, group, P, pad, jac, coef, coef_stride, dy_pred)
-    LTR_DISPATCH_SCHEME(scheme, CALL)
-#undef CALL
-    return launch_status();
+    const int group = pair_group(s_max);
+    return with_scheme(scheme, [&](auto sch) {
+        return launch(lambda_colsum_sys_bwd_ragged_kernel<decltype(sch)::value>, n_queries, group, pair_lds(1, s_max, group), stream,
+                      y_pred, y_true, offsets, queries, n_queries, s_max, n_docs, group, P, pad, jac, coef, coef_stride, dy_pred);
+    });
 }
 
 int64_t ltr_ordinal_num_blocks(int64_t n_docs) { return n_docs <= 0 ? 0 : (n_docs + kOrdBlock - 1) / kOrdBlock; }
@@ -1364,13 +1304,9 @@ int ltr_ordinal_fwd_bwd(const float *y_pred, const float *y_true, int64_t n_docs
     if (!y_pred || !y_true || !block_partials || !sums) return LTR_ERR_NULL;
     if (n_docs < 0 || n < 1 || n > 64 || ltr_ordinal_num_blocks(n_docs) > 0x7fffffff) return LTR_ERR_SHAPE;
     const int64_t nb = ltr_ordinal_num_blocks(n_docs);
-    if (nb > 0) {
-        hipLaunchKernelGGL(ordinal_kernel, ltr_grid(nb), dim3(kOrdBlock), 0, (hipStream_t)stream, y_pred,
-                           y_true, n_docs, n, pad, block_partials, dpred);
-        if (int rc = launch_status()) return rc;
-    }
-    hipLaunchKernelGGL(reduce_pairs_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, block_partials, nb, sums);
-    return launch_status();
+    if (nb > 0)
+        if (int rc = launch(ordinal_kernel, nb, kOrdBlock, 0, stream, y_pred, y_true, n_docs, n, pad, block_partials, dpred)) return rc;
+    return launch(reduce_pairs_kernel, 1, 1024, 0, stream, block_partials, nb, sums);
 }
 
 }  // extern "C"

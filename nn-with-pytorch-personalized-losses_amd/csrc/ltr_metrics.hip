@@ -115,14 +115,10 @@ int ltr_ndcg_at_k(const float *y_true, const float *y_score, int Q, int S, int k
     int block = next_pow2(S);
     block = block < 64 ? 64 : (block > 1024 ? 1024 : block);
     const size_t lds = (size_t)2 * S * sizeof(float);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)ndcg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (int rc = allow_lds(ndcg_kernel, lds)) return rc;
     hipLaunchKernelGGL(ndcg_kernel, ltr_grid(Q), dim3(block), lds, (hipStream_t)stream, y_true, y_score, Q, S, k,
                        gains == LTR_GAINS_EXPONENTIAL ? 1 : 0, no_relevant ? 1.0 : 0.0, reverse_ties ? 1 : 0, ndcg, dcg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LTR_OK : (int)e;
+    return launch_status();
 }
 
 int ltr_ndcg_at_k_ragged(const float *y_true, const float *y_score, const int64_t *offsets, const int32_t *queries, int n_queries,
@@ -137,8 +133,7 @@ int ltr_ndcg_at_k_ragged(const float *y_true, const float *y_score, const int64_
     hipLaunchKernelGGL(ndcg_ragged_kernel, ltr_grid(n_queries), dim3(block), lds, (hipStream_t)stream, y_true, y_score, offsets,
                        queries, n_queries, s_max, k, gains == LTR_GAINS_EXPONENTIAL ? 1 : 0, no_relevant ? 1.0 : 0.0,
                        reverse_ties ? 1 : 0, ndcg, dcg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LTR_OK : (int)e;
+    return launch_status();
 }
 
 }  // extern "C"

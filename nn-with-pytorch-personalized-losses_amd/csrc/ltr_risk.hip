@@ -227,11 +227,6 @@ trisk_tail_kernel(const float *__restrict__ mat, int n_blocks, int block_rows, i
     }
 }
 
-inline int status() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LTR_OK : (int)e;
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The TAIL of a geoRisk / zRisk loss in one launch (riskLosses.py:47-60, :118-125, :170-180, :237-244): the "larger = better" flip
@@ -581,7 +576,7 @@ int ltr_risk_fwd_bwd(const float *mat, int Q, int n_systems, int col, float alph
     if (col < 0 || col >= n_systems || (kind != LTR_RISK_Z && kind != LTR_RISK_GEO)) return LTR_ERR_PARAM;
     hipLaunchKernelGGL(risk_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, mat, Q, n_systems, col, alpha,
                        kind == LTR_RISK_GEO ? 1 : 0, guard, value, dmat);
-    return status();
+    return launch_status();
 }
 
 int ltr_trisk_fwd_bwd(const float *model, const float *baseline, int Q, float alpha, float *value, float *dmodel,
@@ -590,7 +585,7 @@ int ltr_trisk_fwd_bwd(const float *model, const float *baseline, int Q, float al
     if (Q < 1) return LTR_ERR_SHAPE;
     hipLaunchKernelGGL(trisk_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, model, baseline, Q, alpha, value,
                        dmodel, dbaseline);
-    return status();
+    return launch_status();
 }
 
 int ltr_trisk_tail_fwd_bwd(const float *mat, int Q, float alpha, int flip, float factor, float *value, float *dmat, void *stream) {
@@ -598,7 +593,7 @@ int ltr_trisk_tail_fwd_bwd(const float *mat, int Q, float alpha, int flip, float
     if (Q < 1 || Q > (1 << 29)) return LTR_ERR_SHAPE;
     hipLaunchKernelGGL(trisk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, mat, 1, Q, 0, alpha, flip ? 1 : 0, factor,
                        value, dmat);
-    return status();
+    return launch_status();
 }
 
 int ltr_risk_tail_fwd_bwd(const float *mat, int Q, int n_systems, float alpha, int kind, int strategy, int flip, float factor,
@@ -608,8 +603,7 @@ int ltr_risk_tail_fwd_bwd(const float *mat, int Q, int n_systems, float alpha, i
     if ((kind != 0 && kind != 1) || strategy < 1 || strategy > 3) return LTR_ERR_PARAM;
     hipLaunchKernelGGL(risk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, mat, 1, Q, 0, n_systems, alpha, kind, strategy,
                        flip ? 1 : 0, factor, zquirk ? 1 : 0, value, dmat);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LTR_OK : (int)e;
+    return launch_status();
 }
 
 int ltr_risk_tail_blocks_fwd_bwd(const float *blocks, int n_blocks, int block_rows, int n_systems, float alpha, int kind, int strategy,
@@ -621,7 +615,7 @@ int ltr_risk_tail_blocks_fwd_bwd(const float *blocks, int n_blocks, int block_ro
     if ((kind != 0 && kind != 1) || strategy < 1 || strategy > 3) return LTR_ERR_PARAM;
     hipLaunchKernelGGL(risk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, blocks, n_blocks, block_rows, 1, n_systems,
                        alpha, kind, strategy, flip ? 1 : 0, factor, zquirk ? 1 : 0, value, dmat);
-    return status();
+    return launch_status();
 }
 
 int ltr_trisk_tail_blocks_fwd_bwd(const float *blocks, int n_blocks, int block_rows, float alpha, int flip, float factor, float *value,
@@ -630,7 +624,7 @@ int ltr_trisk_tail_blocks_fwd_bwd(const float *blocks, int n_blocks, int block_r
     if (n_blocks < 1 || n_blocks > kMaxRowBlocks || block_rows < 0 || (long long)n_blocks * block_rows > (1 << 29)) return LTR_ERR_SHAPE;
     hipLaunchKernelGGL(trisk_tail_kernel, dim3(1), dim3(kRiskThreads), 0, (hipStream_t)stream, blocks, n_blocks, block_rows, 1, alpha,
                        flip ? 1 : 0, factor, value, dmat);
-    return status();
+    return launch_status();
 }
 
 int ltr_risk_matrix_rows_fwd(const float *ref, const float *x0, const float *rest, int B, int S, int n_rest, int mode, int lt, int ideal,
@@ -641,7 +635,7 @@ int ltr_risk_matrix_rows_fwd(const float *ref, const float *x0, const float *res
     if (B == 0) return LTR_OK;
     hipLaunchKernelGGL(risk_matrix_kernel, dim3(B), dim3(kMatThreads), (size_t)2 * S * sizeof(float), (hipStream_t)stream, ref, x0, rest, B,
                        S, n_rest, mode, lt, ideal ? 1 : 0, ones ? 1 : 0, nullptr, 0, mat, jac);
-    return status();
+    return launch_status();
 }
 
 int ltr_risk_matrix_cached_fwd(const float *ref, const float *x0, const float *cached, int cache_stride, int B, int S, int n_cached,
@@ -652,7 +646,7 @@ int ltr_risk_matrix_cached_fwd(const float *ref, const float *x0, const float *c
     if (B == 0) return LTR_OK;
     hipLaunchKernelGGL(risk_matrix_kernel, dim3(B), dim3(kMatThreads), (size_t)2 * S * sizeof(float), (hipStream_t)stream, ref, x0,
                        cached ? cached : x0, B, S, n_cached, mode, lt, 0, 0, cached ? cached : x0, cache_stride, mat, jac);
-    return status();
+    return launch_status();
 }
 
 int ltr_risk_scores_grad(const float *jac, const float *dmat, int dmat_stride, int B, int S, float *dscores, void *stream) {
@@ -662,7 +656,7 @@ int ltr_risk_scores_grad(const float *jac, const float *dmat, int dmat_stride, i
     const long long blocks = ((long long)B * S + 255) / 256;
     hipLaunchKernelGGL(risk_scores_grad_kernel, ltr_grid(blocks < 4096 ? blocks : 4096), dim3(256), 0, (hipStream_t)stream, jac, dmat,
                        dmat_stride, (long long)B, S, dscores);
-    return status();
+    return launch_status();
 }
 
 int ltr_risk_matrix_fwd(const float *ref, const float *x0, const float *rest, int B, int S, int n_rest, int mode, int lt, int ideal,
@@ -673,8 +667,7 @@ int ltr_risk_matrix_fwd(const float *ref, const float *x0, const float *rest, in
     if (B == 0) return LTR_OK;
     hipLaunchKernelGGL(risk_matrix_kernel, dim3(B), dim3(kMatThreads), (size_t)2 * S * sizeof(float), (hipStream_t)stream, ref, x0, rest, B,
                        S, n_rest, mode, lt, ideal ? 1 : 0, 0, nullptr, 0, mat, jac);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LTR_OK : (int)e;
+    return launch_status();
 }
 
 int ltr_risk_matrix_ragged_fwd(const float *ref, const float *x0, const float *rest, const int64_t *offsets, const int32_t *queries,
@@ -688,7 +681,7 @@ int ltr_risk_matrix_ragged_fwd(const float *ref, const float *x0, const float *r
     hipLaunchKernelGGL(risk_matrix_ragged_kernel, ltr_grid(n_queries), dim3(kMatThreads), (size_t)2 * s_max * sizeof(float),
                        (hipStream_t)stream, ref, x0, cached ? cached : rest, offsets, queries, n_queries, s_max, (long long)n_docs, n_rest,
                        mode, lt, ideal ? 1 : 0, ones ? 1 : 0, cached, cache_stride, mat, jac);
-    return status();
+    return launch_status();
 }
 
 int ltr_risk_scores_grad_ragged(const float *jac, const float *dmat, int dmat_stride, const int64_t *offsets, const int32_t *queries,
@@ -698,7 +691,7 @@ int ltr_risk_scores_grad_ragged(const float *jac, const float *dmat, int dmat_st
     if (n_queries == 0) return LTR_OK;
     hipLaunchKernelGGL(risk_scores_grad_ragged_kernel, ltr_grid(n_queries), dim3(256), 0, (hipStream_t)stream, jac, dmat, dmat_stride,
                        offsets, queries, n_queries, (long long)n_docs, dscores);
-    return status();
+    return launch_status();
 }
 
 }  // extern "C"
