@@ -66,10 +66,6 @@ struct SlateGroup {
     float *red;   // LDS [32]     cross-wave scratch
 };
 
-#ifndef LTR_DPP_REDUCE
-#define LTR_DPP_REDUCE 1
-#endif
-
 // Cross-lane moves inside a 16-lane DPP row (VALU, no LDS crossbar): quad xor-1, quad xor-2, half-row mirror
 // (i <-> 7-i), row mirror (i <-> 15-i).  Each step pairs lanes SYMMETRICALLY, so after the four steps all 16
 // lanes of a row hold bit-identical results for any commutative op.
@@ -86,31 +82,19 @@ __device__ __forceinline__ float lane_bcast(float v, int lane) {
 
 // All-lanes wave reductions; every lane ends with the same bits (replicated control flow depends on it).
 __device__ __forceinline__ float wave_allsum(float v) {
-#if LTR_DPP_REDUCE
     v += LTR_DPP(v, LTR_DPP_XOR1);
     v += LTR_DPP(v, LTR_DPP_XOR2);
     v += LTR_DPP(v, LTR_DPP_HALF_MIRROR);
     v += LTR_DPP(v, LTR_DPP_MIRROR);
     return (lane_bcast(v, 0) + lane_bcast(v, 16)) + (lane_bcast(v, 32) + lane_bcast(v, 48));
-#else
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, LTR_WAVE);
-    return v;  // butterfly: every lane holds the same bits
-#endif
 }
 
 __device__ __forceinline__ float wave_allmax(float v) {
-#if LTR_DPP_REDUCE
     v = fmaxf(v, LTR_DPP(v, LTR_DPP_XOR1));
     v = fmaxf(v, LTR_DPP(v, LTR_DPP_XOR2));
     v = fmaxf(v, LTR_DPP(v, LTR_DPP_HALF_MIRROR));
     v = fmaxf(v, LTR_DPP(v, LTR_DPP_MIRROR));
     return fmaxf(fmaxf(lane_bcast(v, 0), lane_bcast(v, 16)), fmaxf(lane_bcast(v, 32), lane_bcast(v, 48)));
-#else
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, LTR_WAVE));
-    return v;
-#endif
 }
 
 __device__ __forceinline__ float wave_allmin(float v) { return -wave_allmax(-v); }
@@ -143,7 +127,6 @@ __device__ __forceinline__ float group_max(const SlateGroup &g, float v) {
 // The CG replicas of a row are ADJACENT lanes of one wave (t = ri*CG + cg, CG a power of two <= 64), so this
 // is a log2(CG)-step butterfly: no LDS, no barrier, same bits in every replica.
 __device__ __forceinline__ float row_reduce(const SlateGroup &g, float v) {
-#if LTR_DPP_REDUCE
     if (g.CG <= 16) {   // group-uniform
         if (g.CG >= 2) v += LTR_DPP(v, LTR_DPP_XOR1);
         if (g.CG >= 4) v += LTR_DPP(v, LTR_DPP_XOR2);
@@ -151,7 +134,6 @@ __device__ __forceinline__ float row_reduce(const SlateGroup &g, float v) {
         if (g.CG >= 16) v += LTR_DPP(v, LTR_DPP_MIRROR);
         return v;
     }
-#endif
     for (int o = g.CG >> 1; o >= 1; o >>= 1) v += __shfl_xor(v, o, LTR_WAVE);
     return v;
 }

@@ -1671,7 +1671,6 @@ __global__ void __launch_bounds__(kAttThreads) attention_bwd_kernel(AttArgs a) {
         DS[k] = 0.f;
     }
     __syncthreads();
-#ifndef LTR_ATT_SKIP_A      /* timing experiments only */
     for (int qt = w; qt * 16 < a.S; qt += kAttThreads / 64) {
         const int query = 16 * qt + j;
         const long long tok = (long long)b * a.S + query;
@@ -1719,12 +1718,10 @@ __global__ void __launch_bounds__(kAttThreads) attention_bwd_kernel(AttArgs a) {
             for (int dt = 0; dt < 2; ++dt) store4(row, 16 * dt + 4 * g, a.dk, a.dk % 4 == 0, o[dt]);
         }
     }
-#endif
     __syncthreads();
     stage_head(a, b, hd, 0, Sp, img0, tr0, ldt);
     stage_head(a, b, hd, 3, Sp, img1, tr1, ldt);
     __syncthreads();
-#ifndef LTR_ATT_SKIP_B
     for (int kt = w; kt * 16 < a.S; kt += kAttThreads / 64) {
         const int key = 16 * kt + j;
         const long long tok = (long long)b * a.S + key;
@@ -1771,7 +1768,6 @@ __global__ void __launch_bounds__(kAttThreads) attention_bwd_kernel(AttArgs a) {
             }
         }
     }
-#endif
 }
 
 inline size_t att_bwd_lds(int S) {

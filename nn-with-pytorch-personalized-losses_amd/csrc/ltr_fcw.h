@@ -6,7 +6,7 @@
 // The generic pipeline (slate_pipeline_kernel) gives every wave 16 documents and ALL hidden units: every wave then reads every
 // weight, and dz has to be staged through LDS for the document contraction of dW.  Here the HIDDEN UNITS are partitioned instead
 // ("weights-stationary"): a workgroup is 4 waves, wave w owns hidden units 16w .. 16w+15 for all 128 documents of the tile.
-//   * its W1 fragments (hi / lo f16, 5 k-steps: 40 VGPRs) are loaded ONCE per kernel and stay in registers;
+//   * its W1 fragments (hi / lo f16, 5 k-steps: 40 VGPRs) are the only weights it reads: once per tile, from L2 (9 KB per wave);
 //   * fc1 runs NON-transposed, z1[doc][n] = sum_f x[doc][f] W1[n][f]: A = rows of the X image pair in LDS (ds_read_b128, conflict
 //     free), B = the resident fragments; the accumulator tile (row = document, col = hidden unit) of two document tiles IS the A
 //     operand of the weight gradient dW1[n][f] = sum_doc dz1[doc][n] x[doc][f] (k = documents, same k-slot order as the
@@ -19,20 +19,17 @@
 // floats: rows 12 banks apart, so both access patterns below are conflict-free).  For v_mfma_f32_16x16x4_f32 a lane holds ONE
 // value per operand, k-slot = lane >> 4, and the assignment of k-slots to features is free as long as both operands agree:
 //   * fc1 (z1[doc][n], A = x, B = W1): MFMA i of feature group S takes feature 16 S + 4 (lane >> 4) + i, so ONE ds_read_b128 of
-//     a document's row feeds four MFMAs and the resident B fragments are exactly the [64 lanes][4] tiles ltr_mlp_pack writes for
-//     the generic kernel (N::W1F_OFF): 36 VGPRs per wave, loaded once per kernel;
+//     a document's row feeds four MFMAs and the wave's B fragments are exactly the [64 lanes][4] tiles ltr_mlp_pack writes for
+//     the generic kernel (N::W1F_OFF): 36 VGPRs per wave;
 //   * dW1 (A = dz1, B = x): the accumulator tile of fc1 -- lane (n, q) holds documents 4 q + r -- IS the A operand of MFMA r with
 //     k-slot q = document 4 q + r; B is one ds_read_b32 per MFMA, 16 consecutive floats of four rows: conflict-free.
 // 576 MFMAs per wave and tile (18.4 k cycles on its SIMD); no staging of dz through LDS, no weight stream.
 #pragma once
 
-// the sigmoid's reciprocal: v_rcp_f32 (1 ulp) by default.  The backward's h (1 - h) loses RELATIVE accuracy when h is within 1e-4 of
+// The sigmoid's reciprocal is v_rcp_f32 (ltr_rcp, 1 ulp).  The backward's h (1 - h) loses RELATIVE accuracy when h is within 1e-4 of
 // 1, but what the parity metric sees is the absolute error of the gradient contribution, g x 6e-8 -- the size of any other fp32
 // rounding of the step; the correctly rounded division (__frcp_rn: ~10 instructions) bought nothing measurable and cost ~7 % of the
 // folded TripleLayerNet tile (profiles/r04_variant_ab.json)
-#ifndef FCW_SIGMOID_RCP
-#define FCW_SIGMOID_RCP ltr_rcp
-#endif
 #ifdef LTR_STAMPS
 #define FCW_STAMP(k)                                                                                          \
     if (a.stamps && lane == 0 && (st - (int)blockIdx.x) / (int)gridDim.x == a.stamp_tile)                      \
@@ -41,13 +38,6 @@
 #define FCW_STAMP(k)
 #endif
 
-#ifndef FCW_X_PREFETCH
-#define FCW_X_PREFETCH 0           // before the dW1 GEMM of a tile: 1 = the next tile's X rows -> registers (68 VGPRs: spills 356 B/lane,
-                                   // 19.0 -> 12.1 M slates/s), 2 = -> L2 only (17.7 M); 0 = none: both measured SLOWER (profiles/r04_variant_ab.json)
-#endif
-#ifndef FCW_W1_RELOAD
-#define FCW_W1_RELOAD 1            // exact fp32: the W1 fragments are re-read from L2 per tile (9 KB per wave) instead of pinning 36 VGPRs through
-#endif                             // the loss and dW1 phases
 constexpr int kFcwWaves = 4;
 constexpr int kFcwThreads = kFcwWaves * 64;
 
@@ -101,23 +91,12 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
     constexpr int NTW = 8 / N::DS, WPC = kFcwWaves / N::DS;         // document tiles per wave; waves per copy
     const int T0 = N::DS == 1 ? 0 : (w / WPC) * NTW;
 
-    // ---- once per kernel: resident W1 fragments, w3, pads of the X rows, loss scratch
+    // ---- once per kernel: the descriptor of the W1 fragments (re-read per tile), w3, pads of the X rows, loss scratch
     const float w3n = a.packed[N::W3_OFF + n_mine];
     const float b3 = a.packed[N::W3_OFF + N::NT2 * 16];
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.packed), 0, N::PACKED * 4, 0x00020000);
 #if LTR_F16X2
     h16x8 wh[KP], wl[KP];
-#if FCW_W1_RELOAD
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.packed), 0, N::PACKED * 4, 0x00020000);
-#else
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.packed + N::W1B_OFF) + (size_t)w * KP * 2 * 64 + lane;
-#pragma unroll
-        for (int P = 0; P < KP; ++P) {
-            wh[P] = __builtin_bit_cast(h16x8, src[(2 * P) * 64]);
-            wl[P] = __builtin_bit_cast(h16x8, src[(2 * P + 1) * 64]);
-        }
-    }
-#endif
     const float inv_w1 = a.packed[N::W3_OFF + N::NT2 * 16 + 4];
     float w3max = 0.f;
     for (int j = lane; j < N::H2; j += 64) w3max = fmaxf(w3max, fabsf(a.packed[N::W3_OFF + j]));
@@ -131,15 +110,6 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
     int exx = 1, exd = -100, E = -400;
 #else
     f32x4 wf[XT];                                    // lane (n, q): W1aug[16 w + n][16 S + 4 q .. + 3]
-#if FCW_W1_RELOAD
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.packed), 0, N::PACKED * 4, 0x00020000);
-#else
-    {
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(a.packed + N::W1F_OFF) + (size_t)w * XT * 64 + lane;
-#pragma unroll
-        for (int S = 0; S < XT; ++S) wf[S] = src[S * 64];
-    }
-#endif
     for (int e = tid; e < kTileDocs * 4; e += kFcwThreads) Xs[(e >> 2) * LDX + N::F + (e & 3)] = (e & 3) ? 0.f : 1.f;
 #endif
     for (int j = tid; j < kFcwThreads + 4 * 32; j += kFcwThreads) scratch[j] = 0.f;
@@ -189,17 +159,13 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
                 xn[m] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, lane * 16 + m * 1024, 0, 2 /* nt */));
         }
     };
-#if FCW_X_PREFETCH == 1
-    if ((int)blockIdx.x < a.n_super) load_x(blockIdx.x);
-#endif
     for (int st = blockIdx.x; st < a.n_super; st += gridDim.x) {
         const long long doc_base = (long long)st * kTileDocs;
         FCW_STAMP(0)
-        // ---- X: this wave's 32 rows are in flight (or landed) in xn: fetched ahead of time, before the previous tile's dW1 GEMM
-        //      (FCW_X_PREFETCH), so that the HBM latency hides under its MFMAs instead of opening every tile
-#if FCW_X_PREFETCH != 1
+        // ---- X: this wave's 32 rows -> xn, at the top of the tile.  Fetching the next tile ahead of time, before the dW1 GEMM, was
+        //      measured SLOWER both ways: into registers (68 VGPRs: spills 356 B/lane) 19.0 -> 12.1 M slates/s, into L2 only 17.7 M
+        //      (profiles/r04_variant_ab.json)
         load_x(st);
-#endif
 #if LTR_F16X2
         float xm = 0.f;
 #pragma unroll
@@ -208,9 +174,9 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
             for (int r = 0; r < 4; ++r) xm = fmaxf(xm, fabsf(xn[m][r]));
         xm = wave_allmax(xm);
 #endif
-#if FCW_W1_RELOAD
-        {   // this wave's W1 fragments, L2 -> registers, behind the X loads (consumed in fc1, two barriers from here); the byte offset
-            // is laundered per tile so that the loads are not hoisted out of the persistent loop and pinned for the whole kernel
+        {   // this wave's W1 fragments, L2 -> registers (9 KB per wave and tile), behind the X loads (consumed in fc1, two barriers from
+            // here); the byte offset is laundered per tile so that the loads are not hoisted out of the persistent loop and the
+            // fragments pinned (36 VGPRs in the exact version) through the loss and dW1 phases
 #if LTR_F16X2
             int wo = N::W1B_OFF * 4 + w * KP * 2 * 1024;
             asm volatile("" : "+s"(wo));
@@ -226,7 +192,6 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
             for (int S = 0; S < XT; ++S) wf[S] = load_frag(wrs, lane * 16, wo + S * 1024);
 #endif
         }
-#endif
         FCW_STAMP(1)
         __syncthreads();                              // A: every wave is done with the previous tile's images, scores, gradients
 #if LTR_F16X2
@@ -296,7 +261,7 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, wh[P], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, wl[P], acc, 0, 0, 0);
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, wh[P], acc, 0, 0, 0);
-                    if (LTR_LOLO) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, wl[P], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, wl[P], acc, 0, 0, 0);
                 }
                 h1[T] = acc;
                 __builtin_amdgcn_sched_barrier(0);
@@ -348,7 +313,7 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
             for (int r = 0; r < 4; ++r) {
                 float v = h1[T][r] * un;
                 if (N::A1 == ACT_RELU_DROP) v = fmaxf(v, 0.f);
-                else if (N::A1 == ACT_SIGMOID) v = FCW_SIGMOID_RCP(1.f + __expf(-v));
+                else if (N::A1 == ACT_SIGMOID) v = ltr_rcp(1.f + __expf(-v));
                 h1[T][r] = v;
             }
         if (drop) {      // (uniform) training-mode dropout: its own loop, so that the hash arithmetic does not sit in the common path
@@ -448,24 +413,6 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
             }
         }
         FCW_STAMP(8)
-#if FCW_X_PREFETCH == 1
-        if (st + (int)gridDim.x < a.n_super) load_x(st + gridDim.x);      // the next tile's rows: they land under the dW1 MFMAs below
-#elif FCW_X_PREFETCH == 2
-        // pull the NEXT tile of X into L2 while this one is in its dW1 GEMM: one dword per 128-B line per lane (544 lines); the values
-        // are only kept alive until the end of the iteration so that the loads are issued here and waited for there
-        float pf = 0.f;
-        {
-            const long long nb = (long long)(st + gridDim.x) * kTileDocs * N::F;         // first float of the next tile
-            const long long lim = a.n_docs * N::F;
-            if (st + (int)gridDim.x < a.n_super) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const long long fl = nb + ((long long)tid + 256 * k) * 32;
-                    if (tid + 256 * k < (kTileDocs * N::F + 31) / 32 && fl < lim) pf += a.X[fl];
-                }
-            }
-        }
-#endif
 #if LTR_F16X2
         // ---- dW1[n][f] += sum_doc dz1[doc][n] x[doc][f]: A = two accumulator tiles of dz1 (split in registers), B = x k-major
         {
@@ -486,7 +433,7 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
                     accW[Ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bh, accW[Ti], 0, 0, 0);
                     accW[Ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bl, accW[Ti], 0, 0, 0);
                     accW[Ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bh, accW[Ti], 0, 0, 0);
-                    if (LTR_LOLO) accW[Ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bl, accW[Ti], 0, 0, 0);
+                    accW[Ti] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bl, accW[Ti], 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -525,9 +472,6 @@ __global__ void __launch_bounds__(kFcwThreads, 2) fcw_fused_kernel(const PipeArg
         }
 #endif
         FCW_STAMP(9)
-#if FCW_X_PREFETCH == 2
-        asm volatile("" ::"v"(pf));   // keep the prefetch loads alive (and waited for) until here
-#endif
     }
     // ---- per-workgroup partial gradients -> workspace (the layout reduce_grads_kernel<N> sums)
     float *out = a.partials + (size_t)blockIdx.x * N::PART;

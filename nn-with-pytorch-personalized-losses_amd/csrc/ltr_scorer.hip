@@ -29,19 +29,22 @@
 #include <type_traits>
 
 
+// Build-time switches of this file and ltr_fcw.h (every other experiment is retired at its measured value: DESIGN.md 4.2e):
+//   LTR_F16X2 = 1                the shipped variant library, passed by ltr_mi355x/build.py
+//   LTR_STAMPS, LTR_STAMPS_DW    phase stamps, passed by hand through tools/build_variant.sh for tools/phase_stamps.py / fcw_stamps.py
+//   LTR_DIAG                     phase ablation (PipeArgs::debug_skip), passed the same way for tools/bench_phases.py
+//
 // LTR_F16X2 = 1 builds the f16 x 2 split variant (libltr_mi355x_f16x2.so, same C ABI): fc1 / fc2 / dh1 -- the GEMMs whose
 // B operand lives in the wave's registers -- run on v_mfma_f32_16x16x32_f16 with every fp32 operand split into two f16
-// pieces (hi + lo, power-of-two pre-scaling per document / per weight matrix / running maximum) and the piece products
-// (hi hi, hi lo, lo hi and -- LTR_LOLO -- lo lo) accumulated in fp32; the weight-gradient GEMMs run the same way on f16 image
-// pairs staged in LDS.  4 B per element like fp32, 16/4 = 4 x the fp32 matrix rate.  See DESIGN.md section 4.3.
+// pieces (hi + lo, power-of-two pre-scaling per document / per weight matrix / running maximum) and all FOUR piece products
+// (hi hi, hi lo, lo hi, lo lo) accumulated in fp32; the weight-gradient GEMMs run the same way on f16 image pairs staged in
+// LDS.  4 B per element like fp32, 16/4 = 4 x the fp32 matrix rate.  See DESIGN.md section 4.3.
+// With the lo lo term the product of the split operands is exact and the error is the operands' 2^-22 representation alone.  The
+// matrix pipe has the slack (the FC GEMMs are bound by weight-fragment bandwidth, the dW GEMMs by LDS latency); with three
+// products the cancelling bias gradients of a 48-document golden missed the 1e-5 bar by 6 %.
 #ifndef LTR_F16X2
 #define LTR_F16X2 0
 #endif
-#ifndef LTR_LOLO
-#define LTR_LOLO 1               // 1: all FOUR piece products (the lo lo term too): the product of the split operands is then exact and
-#endif                           //    the error is the operands' 2^-22 representation alone.  The matrix pipe has the slack (the FC GEMMs
-                                 //    are bound by weight-fragment bandwidth, the dW GEMMs by LDS latency); with three products the
-                                 //    cancelling bias gradients of a 48-document golden missed the 1e-5 bar by 6 %.
 
 using namespace ltr;
 
@@ -53,10 +56,7 @@ constexpr int kTileDocs = 128;   // documents per super-tile
 constexpr int kWaves = 8;        // 2 waves per SIMD: the co-resident wave hides LDS / L2 latency
 constexpr int kThreads = kWaves * 64;
 constexpr int kChunkDocs = 64;   // documents per dW staging chunk (the 16-doc tiles of 4 waves)
-#ifndef LTR_RING
-#define LTR_RING 6
-#endif
-constexpr int kRing = LTR_RING;  // weight fragments kept in flight per wave (1 KiB each, L2 -> registers)
+constexpr int kRing = 6;         // weight fragments kept in flight per wave (1 KiB each, L2 -> registers)
 // Next-X-tile prefetch policy, per kernel instantiation (A/B on MI355X, profiles/r01_variant_ab.json):
 //   registers (36 VGPRs live across the loop) where they are free: forward-only kernels -8..-19 %, the 136-64-32
 //   net's fused kernel -4 %;  L2-only prefetch (one dword per 128-B line) for the 136-136-136 backward/fused
@@ -214,25 +214,12 @@ __device__ __forceinline__ unsigned keep_word(unsigned long long seed, int layer
     return keep_word_at(keep_prefix(seed, layer, doc), word);
 }
 
-// Sum over the 16 lanes of a DPP row (= the 16 documents sharing one q); the total lands in lane 15 of the row.
-__device__ __forceinline__ float row_sum_to_lane15(float v) {
-#define LTR_DPP_SHR(x, n) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x110 + (n), 0xF, 0xF, true))
-    v += LTR_DPP_SHR(v, 1);
-    v += LTR_DPP_SHR(v, 2);
-    v += LTR_DPP_SHR(v, 4);
-    v += LTR_DPP_SHR(v, 8);
-#undef LTR_DPP_SHR
-    return v;
-}
-// The same for FOUR values at once, every step as ONE v_add_f32_dpp: hipcc fuses only the row_shr:2 / :4 steps of the form above and
+// Sum over the 16 lanes of a DPP row (= the 16 documents sharing one q) for FOUR values at once; the totals land in lane 15 of the
+// row.  Every step is ONE v_add_f32_dpp: written with __builtin_amdgcn_update_dpp, hipcc fuses only the row_shr:2 / :4 steps and
 // expands the other two into copy + v_mov_b32_dpp + v_add_f32 (two extra instructions per step and value, in kernels whose non-matrix
 // time is instruction count).  The four chains are interleaved, so a DPP read is always >= 3 instructions behind the write of its
 // source (the hardware wants 2 wait states); the leading s_nop covers the caller's last write.
-#ifndef LTR_ROWSUM_ASM
-#define LTR_ROWSUM_ASM 1
-#endif
 __device__ __forceinline__ f32x4 row_sum4_to_lane15(f32x4 v) {
-#if LTR_ROWSUM_ASM
     float a = v[0], b = v[1], c = v[2], d = v[3];
 #define LTR_ROWSUM_STEP(n)                                                                  \
     "v_add_f32_dpp %0, %0, %0 row_shr:" #n " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"   \
@@ -242,9 +229,6 @@ __device__ __forceinline__ f32x4 row_sum4_to_lane15(f32x4 v) {
     asm("s_nop 1\n\t" LTR_ROWSUM_STEP(1) LTR_ROWSUM_STEP(2) LTR_ROWSUM_STEP(4) LTR_ROWSUM_STEP(8) : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
 #undef LTR_ROWSUM_STEP
     return f32x4{a, b, c, d};
-#else
-    return f32x4{row_sum_to_lane15(v[0]), row_sum_to_lane15(v[1]), row_sum_to_lane15(v[2]), row_sum_to_lane15(v[3])};
-#endif
 }
 
 // z^T tiles = W fragments x B fragments for the wave's 16-document tile.
@@ -307,9 +291,7 @@ __device__ __forceinline__ void gemm_wx(__amdgpu_buffer_rsrc_t rsrc, int base_by
 
 #if LTR_F16X2
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-#ifndef LTR_RING_H
-#define LTR_RING_H 8             // 16-byte fragment pieces in flight per wave (hi and lo of 4 (k-step, tile) pairs)
-#endif
+constexpr int kRingH = 8;        // 16-byte fragment pieces in flight per wave (hi and lo of 4 (k-step, tile) pairs)
 
 // The f16 x 2 form of gemm_wx: out^T tiles = W x B with B = the wave's activation tiles `bin` (accumulator layout).
 // k-step P covers input tiles 2P and 2P+1: element j of lane (q, d) is feature 16 (2P + (j >> 2)) + 4q + (j & 3) -- the
@@ -323,7 +305,7 @@ __device__ __forceinline__ void gemm_wx_h(__amdgpu_buffer_rsrc_t rsrc, int base_
     constexpr int KP = (KT + 1) / 2;
     constexpr int NSTEP = KP * NT;
     constexpr int NLOAD = 2 * NSTEP;
-    constexpr int R = LTR_RING_H;
+    constexpr int R = kRingH;
     static_assert(R % 2 == 0, "hi and lo pieces travel together");
     f32x4 ring[R];
 #pragma unroll
@@ -364,7 +346,7 @@ __device__ __forceinline__ void gemm_wx_h(__amdgpu_buffer_rsrc_t rsrc, int base_
         out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, out[To], 0, 0, 0);
         out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, out[To], 0, 0, 0);
         out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, out[To], 0, 0, 0);
-        if (LTR_LOLO) out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, blo, out[To], 0, 0, 0);
+        out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, blo, out[To], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -487,13 +469,6 @@ struct DwSet {   // which A (row) / B (column) fragments wave W's tile set touch
             if (dw_col<NR, NC, BH>(first + j) == Ti) return true;
         return false;
     }
-    static constexpr int n_frags() {
-        int n = 0;
-        for (int t = 0; t < NR; ++t) n += uses_row(t) ? 1 : 0;
-        for (int t = 0; t < NC; ++t) n += uses_col(t) ? 1 : 0;
-        return n;
-    }
-    static constexpr int n_tiles() { return count; }
 };
 
 template <int W, int TW, int NR, int NC, int BH, int LD>
@@ -515,63 +490,17 @@ __device__ __forceinline__ void dw_mfma(f32x4 (&acc)[TW], const float (&af)[NR],
     }
 }
 
-#ifndef LTR_DW_PIPE
-#define LTR_DW_PIPE 0
-#endif
-#ifndef LTR_PRIO
-#define LTR_PRIO 0               // 1: s_setprio 1 for waves 4-7 (A/B experiment)
-#endif
-#ifndef LTR_KROT
-#define LTR_KROT 0               // 1: waves 4-7 walk the dW k steps half a chunk out of phase (A/B experiment)
-#endif
-#ifndef LTR_H1_BITS
-#define LTR_H1_BITS 0
-#endif
-#ifndef LTR_STG_SWZ
-#define LTR_STG_SWZ 0            // 1: XOR-swizzled dW staging images (A/B experiment): row r keeps its 4-float pieces at
-#endif                           //    position (4 q) ^ 4 ((r >> 1) & 3) inside each 16-feature tile -> 2-way instead of 8-way
-                                 //    conflicted ds_write_b128; fragment reads use two lane bases (even / odd k steps)
-
+// a_odd / b_odd: lane bases of the odd k-steps.  Every caller's are its a_base / b_base again (they served XOR-swizzled staging
+// images, measured and retired: DESIGN.md 4.2e); the pair stays because the dW1 call has to spell its bases out twice (see there).
 template <int W, int TW, int NR, int NC, int BH, int LD>
 __device__ __forceinline__ void dw_chunk_w(f32x4 (&acc)[TW], const float *a_base, const float *b_base, const float *a_odd,
                                            const float *b_odd) {
     constexpr int KS = kChunkDocs / 4;
-#if LTR_DW_PIPE
-    static_assert(!LTR_STG_SWZ, "the pipelined variant reads unswizzled images");
-    // Fragments double-buffered and the interleave PINNED (one LDS read per MFMA): the reads of k-step s+1 are in
-    // flight under the MFMAs of k-step s.  (Left to itself hipcc sinks the reads next to their use and waits
-    // lgkmcnt(0) every 5-6 MFMAs.)
-    constexpr int NF = DwSet<W, TW, NR, NC, BH>::n_frags();
-    constexpr int NM = DwSet<W, TW, NR, NC, BH>::n_tiles();
-    float af0[NR], bf0[NC], af1[NR], bf1[NC];
-    dw_load<W, TW, NR, NC, BH, LD>(af0, bf0, a_base, b_base);
-#pragma unroll
-    for (int s = 0; s < KS; s += 2) {
-        dw_load<W, TW, NR, NC, BH, LD>(af1, bf1, a_base + (s + 1) * 4 * LD, b_base + (s + 1) * 4 * LD);
-        dw_mfma<W, TW, NR, NC, BH>(acc, af0, bf0);
-#pragma unroll
-        for (int i = 0; i < (NM > NF ? NM : NF); ++i) {
-            if (i < NF) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 DS read
-            if (i < NM) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-        }
-        if (s + 2 < KS)
-            dw_load<W, TW, NR, NC, BH, LD>(af0, bf0, a_base + (s + 2) * 4 * LD, b_base + (s + 2) * 4 * LD);
-        dw_mfma<W, TW, NR, NC, BH>(acc, af1, bf1);
-#pragma unroll
-        for (int i = 0; i < (NM > NF ? NM : NF); ++i) {
-            if (i < NF && s + 2 < KS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            if (i < NM) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-    }
-#else
-    for (int s0 = 0; s0 < KS; ++s0) {
-        // LTR_KROT: the second half of the workgroup walks the k steps half a chunk out of phase with its SIMD partner
-        const int s = LTR_KROT ? ((s0 + (W >= kWaves / 2 ? KS / 2 : 0)) % KS) : s0;
+    for (int s = 0; s < KS; ++s) {
         float af[NR], bf[NC];
         dw_load<W, TW, NR, NC, BH, LD>(af, bf, ((s & 1) ? a_odd : a_base) + s * 4 * LD, ((s & 1) ? b_odd : b_base) + s * 4 * LD);
         dw_mfma<W, TW, NR, NC, BH>(acc, af, bf);
     }
-#endif
 }
 
 template <int TW, int NR, int NC, int BH, int LD>
@@ -658,7 +587,7 @@ __device__ __forceinline__ void dw_chunk_h_w(f32x4 (&acc)[TW], const uint16_t *a
                         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], bh, acc[j], 0, 0, 0);
                         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], bl, acc[j], 0, 0, 0);
                         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[r], bh, acc[j], 0, 0, 0);
-                        if (LTR_LOLO) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[r], bl, acc[j], 0, 0, 0);
+                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[r], bl, acc[j], 0, 0, 0);
                     }
                 }
             }
@@ -685,7 +614,7 @@ template <int NT, int KT, int LDH, int NMAX>
 __device__ __forceinline__ void gemm_wx_hx(__amdgpu_buffer_rsrc_t rsrc, int base_bytes, int lane_off, const uint16_t *xhi_row,
                                            const uint16_t *xlo_row, f32x4 (&out)[NMAX], float un) {
     constexpr int KP = (KT + 1) / 2;
-    constexpr int NSTEP = KP * NT, NLOAD = 2 * NSTEP, R = LTR_RING_H;
+    constexpr int NSTEP = KP * NT, NLOAD = 2 * NSTEP, R = kRingH;
     f32x4 ring[R];
 #pragma unroll
     for (int n = 0; n < R; ++n)
@@ -711,7 +640,7 @@ __device__ __forceinline__ void gemm_wx_hx(__amdgpu_buffer_rsrc_t rsrc, int base
         out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, out[To], 0, 0, 0);
         out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, out[To], 0, 0, 0);
         out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, out[To], 0, 0, 0);
-        if (LTR_LOLO) out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, blo, out[To], 0, 0, 0);
+        out[To] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, blo, out[To], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -781,22 +710,9 @@ __device__ __forceinline__ void load_x_tile(f32x4 (&xr)[kXV4<N>()], const PipeAr
     }
 }
 
-#ifndef LTR_LOSS_UNR
-#define LTR_LOSS_UNR 1           // trips of 8 columns unrolled in the approxNDCG sweeps of the 136-wide nets: 2 costs 72 B/lane more scratch and 2 % (profiles/r03_variant_ab.json)
-#endif
-#ifndef LTR_XDMA
-#define LTR_XDMA 1
-#endif
-#ifndef LTR_PIPE_ST128_MAXH
-#define LTR_PIPE_ST128_MAXH 64      // widest first hidden layer that gets the slate-128 instantiation (A/B: profiles/r04_variant_ab.json)
-#endif
-#ifndef LTR_PIPE_ST128
-#define LTR_PIPE_ST128 1          // a slate-128 instantiation of the fused approxNDCG pipeline kernels (one loss copy with fixed geometry)
-#endif
-#ifndef LTR_X_AUX
-#define LTR_X_AUX 2              // cache policy of the X stream: 2 = nt (read once by one CU: keeps the L2-resident weight
-                                 // fragments from being evicted; FETCH_SIZE -16 % at equal time), 0 = default
-#endif
+// cache policy of the X stream: 2 = nt (read once by one CU: keeps the L2-resident weight fragments from being evicted;
+// FETCH_SIZE -16 % at equal time against 0 = default)
+constexpr int kXAux = 2;
 // X: HBM/L2 -> LDS by LDS-DMA (global_load_lds, 16 B per lane, no VGPRs, no address math): one wave-instruction
 // per document row, lanes 0..F/4-1 active, destination = row base + lane*16 (rows keep their padded LD stride;
 // the pad columns -- ones feature + zeros -- are constant and written once per kernel).  Rows past the end of
@@ -812,7 +728,7 @@ __device__ __forceinline__ void dma_x_rows(const PipeArgs &a, float *Xs, long lo
         float *dst = Xs + (16 * w + r) * N::LD;                 // wave-uniform
         if (row0 + r < a.n_docs) {                               // wave-uniform
             if (lane < N::F / 4)
-                __builtin_amdgcn_global_load_lds((gptr_t)(a.X + (row0 + r) * N::F + 4 * lane), (lptr_t)dst, 16, 0, LTR_X_AUX);
+                __builtin_amdgcn_global_load_lds((gptr_t)(a.X + (row0 + r) * N::F + 4 * lane), (lptr_t)dst, 16, 0, kXAux);
         } else if (lane < N::F / 4) {
             *reinterpret_cast<f32x4 *>(dst + 4 * lane) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -831,10 +747,10 @@ __device__ __forceinline__ void dw2_chunks(int w, int chunk, int crow, int q, in
         if (chunk == c) {
 #pragma unroll
             for (int To = 0; To < N::NT2; ++To)
-                *reinterpret_cast<f32x4 *>(Ds + crow * LD + 16 * To + ((4 * q) ^ (LTR_STG_SWZ ? 4 * ((crow >> 1) & 3) : 0))) = dz2[To];
+                *reinterpret_cast<f32x4 *>(Ds + crow * LD + 16 * To + 4 * q) = dz2[To];
 #pragma unroll
             for (int T = 0; T < N::H1T; ++T)
-                *reinterpret_cast<f32x4 *>(Hs + crow * LD + 16 * T + ((4 * q) ^ (LTR_STG_SWZ ? 4 * ((crow >> 1) & 3) : 0))) = h1[T];
+                *reinterpret_cast<f32x4 *>(Hs + crow * LD + 16 * T + 4 * q) = h1[T];
         }
 #ifdef LTR_STAMPS_DW
         stamp(c == 0 ? 10 : 13);
@@ -843,10 +759,7 @@ __device__ __forceinline__ void dw2_chunks(int w, int chunk, int crow, int q, in
 #ifdef LTR_STAMPS_DW
         stamp(c == 0 ? 11 : 14);
 #endif
-        dw_chunk<N::TW2, N::NT2, N::H1T, N::BH2, LD>(w, acc, Ds + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (q >> 1) : 0)),
-                                                     Hs + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (q >> 1) : 0)),
-                                                     Ds + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (2 + (q >> 1)) : 0)),
-                                                     Hs + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (2 + (q >> 1)) : 0)));
+        dw_chunk<N::TW2, N::NT2, N::H1T, N::BH2, LD>(w, acc, Ds + q * LD + d, Hs + q * LD + d);
 #ifdef LTR_STAMPS_DW
         if (c == 0) stamp(12);
 #endif
@@ -889,11 +802,6 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.packed), 0, N::PACKED * 4, 0x00020000);
     const int lane_off = lane * 16;
 
-#if LTR_PRIO
-    // static priority for the second-dispatched half of the workgroup (the arbitration loser on every segment when the
-    // two waves of a SIMD run the same program): MI355X_MICROARCH.md, "Two waves per SIMD", item 4
-    if (w >= kWaves / 2) __builtin_amdgcn_s_setprio(1);
-#endif
     for (int j = tid; j < N::NT2 * 16 + 16; j += kThreads) w3s[j] = a.packed[N::W3_OFF + j];
     for (int j = tid; j < kWaves * N::NT2 * 16; j += kThreads) dw3[j] = 0.f;
     for (int j = tid; j < kThreads + 4 * 32; j += kThreads) scratch[j] = 0.f;   // slate-group scratch (ListNet / LambdaLoss groups; approxNDCG: [0, 128) wave partials)
@@ -914,12 +822,9 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
     const int crow = 16 * (w & 3) + d;                     // ... and its row inside the chunk
 
     constexpr bool XPREF = x_reg_prefetch<N, MODE>();
-    constexpr bool XDMA = LTR_XDMA && !XPREF;
+    constexpr bool XDMA = !XPREF;
 #if LTR_F16X2
-#ifndef LTR_DWH
-#define LTR_DWH 1                // 1: the weight-gradient GEMMs on the f16 matrix cores too (step 3)
-#endif
-    constexpr bool DWH = LTR_DWH && MODE != MODE_FWD && (XDMA || XPREF);
+    constexpr bool DWH = MODE != MODE_FWD;                             // the weight-gradient GEMMs on the f16 matrix cores too (step 3)
     constexpr int LDH = LD;                                            // halfs per row of an f16 image (LD / 2 dwords: 8 mod 64 at LD = 144)
     uint16_t *Xhi = reinterpret_cast<uint16_t *>(Xs), *Xlo = Xhi + kTileDocs * LDH;   // X as hi / lo images: the bytes of the fp32 tile
     uint16_t *Sg = reinterpret_cast<uint16_t *>(Ds);                   // staging images (and the landing zone of the X DMA)
@@ -934,10 +839,7 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
     // then only waits for it.  Every dW tile still sums its documents in the same order (chunk 0, then chunk 1), so no result
     // bit changes.  The fence of the first dW2 __syncthreads() waits for the DMA, so it lands under the chunk-0 staging; an
     // LDS-only barrier there was measured 0.3 % slower.
-#ifndef LTR_REORD
-#define LTR_REORD 1
-#endif
-    constexpr bool REORD = LTR_REORD && XDMA && !N::TWO && !DWH && MODE != MODE_FWD;
+    constexpr bool REORD = XDMA && !N::TWO && !DWH && MODE != MODE_FWD;
     f32x4 xn[kXV4<N>()];
 #if LTR_F16X2
     if (DWH) {    // zero pad columns of both X images (the ones feature at column F is rewritten per tile: it carries the scale)
@@ -1041,7 +943,7 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else {
             // register-prefetch kernels: only the first tile is loaded here, later ones arrive ahead of time
-            if (!XPREF || st == (int)blockIdx.x) load_x_tile<N>(xn, a, doc_base + 16 * w, lane);
+            if (st == (int)blockIdx.x) load_x_tile<N>(xn, a, doc_base + 16 * w, lane);
             constexpr int V4_PER_ROW = N::F / 4;
             constexpr int V4 = 16 * V4_PER_ROW;             // float4s per wave
 #pragma unroll
@@ -1263,19 +1165,6 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
             }
         }
         // h2 now holds dz2.
-#if LTR_H1_BITS
-        // From here on h1 is needed as a VALUE only by the dW2 staging; the dz1 mask needs just sign(h1) for
-        // ReLU layers: keep NT1*4 sign bits (2 VGPRs) so the 36 h1 registers are dead during the dh1 GEMM,
-        // the register-pressure peak of the kernel.
-        unsigned hbits[(N::NT1 * 4 + 31) / 32] = {};
-        if (N::A1 == ACT_RELU_DROP) {
-#pragma unroll
-            for (int To = 0; To < N::NT1; ++To)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    hbits[(To * 4 + r) >> 5] |= (h1[To][r] > 0.f ? 1u : 0u) << ((To * 4 + r) & 31);
-        }
-#endif
         LTR_STAMP(6)
         auto stamp_dw = [&](int k) { LTR_STAMP(k) };
 #if LTR_F16X2
@@ -1348,13 +1237,7 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float gsc = (N::A1 == ACT_RELU_DROP) ? dz1[To][r] * slope : dz1[To][r];
-#if LTR_H1_BITS
-                float v = (N::A1 == ACT_RELU_DROP)
-                              ? (((hbits[(To * 4 + r) >> 5] >> ((To * 4 + r) & 31)) & 1u) ? gsc : 0.f)
-                              : apply_act_grad<N::A1>(gsc, h1[To][r]);
-#else
                 float v = apply_act_grad<N::A1>(gsc, h1[To][r]);
-#endif
                 if (16 * To + 16 > N::H1) v = (16 * To + 4 * q + r < N::H1) ? v : 0.f;   // last tile only
                 dz1[To][r] = v;
             }
@@ -1399,41 +1282,24 @@ __global__ void __launch_bounds__(kThreads, 2) slate_pipeline_kernel(const PipeA
         if (MODE != MODE_FWD && XPREF && st + (int)gridDim.x < a.n_super)
             load_x_tile<N>(xn, a, (long long)(st + gridDim.x) * kTileDocs + 16 * w, lane);
         // ---- dW1 += dz1^T [x | 1]; B operand straight from the X tile in LDS.
-#ifndef LTR_DW1_SINGLE
-#define LTR_DW1_SINGLE 1    // all nets: dz1 of the whole tile staged at once (one barrier pair instead of two; -1 % on the backward)
-#endif
-        if (N::H1 <= 64 || LTR_DW1_SINGLE) {
+        {
             // dW2 is done with the two staging buffers, which are contiguous (Ds..Hs = one [128][LD] region): every
-            // wave stages its dz1 tile at once, one barrier, then both 64-document halves back to back.  (-3.5 % on
-            // the 136-64-32 net; on the register-bound 136-136-136 kernels the chunked form below is faster.)
+            // wave stages its dz1 tile at once, one barrier, then both 64-document halves back to back: one barrier
+            // pair instead of the two of staging chunk by chunk (-3.5 % on the 136-64-32 net, -1 % on the backward
+            // of the others).
             if (!REORD) __syncthreads();  // every wave is done reading Ds / Hs (dW2 chunk 1)
 #pragma unroll
             for (int To = 0; To < N::NT1; ++To)
-                *reinterpret_cast<f32x4 *>(Ds + my_row * LD + 16 * To + ((4 * q) ^ (LTR_STG_SWZ ? 4 * ((my_row >> 1) & 3) : 0))) = dz1[To];
+                *reinterpret_cast<f32x4 *>(Ds + my_row * LD + 16 * To + 4 * q) = dz1[To];
             __syncthreads();
             if (!LTR_SKIP(a, 2)) {
+                // Both bases are written out twice (as a_odd / b_odd of dw_chunk) on purpose: hipcc's output depends on it.  Passed
+                // once, the 136-64-32 net's backward and fused kernels come out with their accumulator-zeroing v_movs in another
+                // order -- same instruction count, but no longer the code that was measured.
 #pragma unroll
                 for (int c = 0; c < 2; ++c)
-                    dw_chunk<N::TW1, N::NT1, N::XT, N::BH1, LD>(w, accW1, Ds + (64 * c + q) * LD + (d ^ (LTR_STG_SWZ ? 4 * (q >> 1) : 0)),
-                                                                Xs + (64 * c + q) * LD + d,
-                                                                Ds + (64 * c + q) * LD + (d ^ (LTR_STG_SWZ ? 4 * (2 + (q >> 1)) : 0)),
-                                                                Xs + (64 * c + q) * LD + d);
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                __syncthreads();              // previous chunk's readers are done with Ds
-                if (chunk == c) {
-#pragma unroll
-                    for (int To = 0; To < N::NT1; ++To)
-                        *reinterpret_cast<f32x4 *>(Ds + crow * LD + 16 * To + ((4 * q) ^ (LTR_STG_SWZ ? 4 * ((crow >> 1) & 3) : 0))) = dz1[To];
-                }
-                __syncthreads();
-                if (!LTR_SKIP(a, 2))
-                    dw_chunk<N::TW1, N::NT1, N::XT, N::BH1, LD>(w, accW1, Ds + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (q >> 1) : 0)),
-                                                                Xs + (64 * c + q) * LD + d,
-                                                                Ds + q * LD + (d ^ (LTR_STG_SWZ ? 4 * (2 + (q >> 1)) : 0)),
-                                                                Xs + (64 * c + q) * LD + d);
+                    dw_chunk<N::TW1, N::NT1, N::XT, N::BH1, LD>(w, accW1, Ds + (64 * c + q) * LD + d, Xs + (64 * c + q) * LD + d,
+                                                                Ds + (64 * c + q) * LD + d, Xs + (64 * c + q) * LD + d);
             }
         }
         if (REORD) {
@@ -1740,7 +1606,7 @@ int pipeline_dispatch(int mode, const PipeArgs &a, int grid, hipStream_t stream)
                         // a slate-128 instantiation (ONE copy of the loss, fixed geometry) for the narrow nets: 136-64-32 +10.6 %; the
                         // 136-wide kernels, at their register limit, allocate better with the run-time form (0.594 vs 0.579 of the fp32
                         // MFMA peak; profiles/r04_variant_ab.json)
-                        if constexpr (LTR_PIPE_ST128 && N::H1 <= LTR_PIPE_ST128_MAXH) {
+                        if constexpr (N::H1 <= 64) {
                             if (a.S == 128) return launch_pipeline<N, MODE_FUSED, 0, 128>(a, grid, stream);
                         }
                         return launch_pipeline<N, MODE_FUSED, 0, 0>(a, grid, stream);

@@ -1,8 +1,8 @@
 """Build libltr_mi355x.so (and its split-precision variant) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
   libltr_mi355x.so        exact fp32 slate pipeline (v_mfma_f32_16x16x4_f32)                    -- the default library
-  libltr_mi355x_f16x2.so  same C ABI; the FC scorer GEMMs of the slate pipeline as two-piece f16 splits (hi + lo, three of
-                          the four piece products) on v_mfma_f32_16x16x32_f16 with fp32 accumulation (-DLTR_F16X2=1);
+  libltr_mi355x_f16x2.so  same C ABI; the FC scorer GEMMs of the slate pipeline as two-piece f16 splits (hi + lo, all four
+                          piece products) on v_mfma_f32_16x16x32_f16 with fp32 accumulation (-DLTR_F16X2=1);
                           selected with LTR_LIB=<path> (ltr_mi355x._lib).  Only csrc/ltr_scorer.hip differs.
 """
 import glob
