@@ -490,6 +490,41 @@ int ltr_svmlight_load(const char *path, int64_t n_docs, int n_features, int feat
 int ltr_gather_rows_f32(const float *src, int64_t src_rows, const int64_t *idx, int64_t n_rows, int64_t row_floats,
                         float *dst, void *stream);
 
+/* ---- data.slate_length (config.json) / fixed-length slates from a ragged collection          utils/dataset.py:44-69
+ * The reference keeps per-query lists (dataset.py:44-69) and its config carries data.slate_length = 100, the allRank rule: every
+ * query becomes one slate of S documents, a longer query sub-sampled (anew each epoch), a shorter one padded with label -1.  Here
+ * that step runs on the device.  offsets / queries / n_queries as for the ragged loss launches above (queries == NULL: 0 ..
+ * n_queries - 1); a query has len = 1 .. LTR_MAX_SLATE documents, 1 <= S <= LTR_MAX_SLATE.  One 256-thread workgroup per listed query.
+ *
+ * ltr_slates_select: rows [n_queries][S] (int64) and, when non-NULL, mask [n_queries][S] (bytes), every entry written.  Listed
+ *   query i (id q) keeps k = min(len, S) documents: LTR_SLATES_FIRST its first k; LTR_SLATES_SAMPLE all of them when len <= S, else
+ *   the S documents with the smallest 64-bit key (ties: the lower index), the key of local document j being, mod 2^64,
+ *       z = seed ^ (q * 0xD1B54A32D192ED03 + j * 0x9E3779B97F4A7C15 + 0x8CB92BA72F3D8DD7)
+ *       z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  key = z ^ (z >> 31)
+ *   (ranks by counting over the keys in LDS, as the loss kernels rank scores).  The kept documents fill slots 0 .. k - 1 in
+ *   ascending document order: rows[i][slot] = offsets[q] + j, mask 0; slots k .. S - 1: rows -1, mask 1 (1 = padded, the
+ *   convention of the encoder's padding masks).  A listed query whose length is outside 1 .. LTR_MAX_SLATE gets S padding slots.
+ * ltr_slates_gather_f32: dst[i][:] = src[rows[i]][:] when 0 <= rows[i] < src_rows, else the whole row = fill (a negative index
+ *   does NOT count from the end: the difference from ltr_gather_rows_f32).  Copies keep every bit (NaN payloads, -0.0).
+ * ltr_slates_scatter_f32: dst[rows[i]][:] = src[i][:] for 0 <= rows[i] < dst_rows; every other dst row is left untouched.  No
+ *   atomics: the caller's rows name no destination twice (select / build never repeat a non-negative row).
+ *   Both: 16-byte-per-lane copies when row_floats % 4 == 0 and both bases are 16-byte aligned, else 4-byte ones.
+ * ltr_slates_build: the per-batch path in ONE launch -- the selection, X_out [n_queries * S][F] (zero rows in padding slots),
+ *   y_out [n_queries * S] (`pad` in padding slots), and mask / rows as ltr_slates_select writes them (either may be NULL).  Bitwise
+ *   ltr_slates_select followed by ltr_slates_gather_f32 on X (fill 0) and on y (fill pad).  16-byte copies when F % 4 == 0 and X,
+ *   X_out are 16-byte aligned, else 4-byte ones.  F <= 2^20.
+ * NULL required pointer: LTR_ERR_NULL; n_queries < 0, S outside 1 .. LTR_MAX_SLATE, F or row_floats < 1, a negative count:
+ * LTR_ERR_SHAPE; unknown mode: LTR_ERR_PARAM; then a count of 0 returns LTR_OK without a launch. */
+enum { LTR_SLATES_FIRST = 0, LTR_SLATES_SAMPLE = 1 };
+int ltr_slates_select(const int64_t *offsets, const int32_t *queries, int n_queries, int S, int mode, uint64_t seed, int64_t *rows,
+                      uint8_t *mask, void *stream);
+int ltr_slates_gather_f32(const float *src, int64_t src_rows, const int64_t *rows, int64_t n_slots, int64_t row_floats, float fill,
+                          float *dst, void *stream);
+int ltr_slates_scatter_f32(const float *src, const int64_t *rows, int64_t n_slots, int64_t row_floats, int64_t dst_rows, float *dst,
+                           void *stream);
+int ltr_slates_build(const float *X, const float *y, const int64_t *offsets, const int32_t *queries, int n_queries, int S, int F,
+                     int mode, uint64_t seed, float pad, float *X_out, float *y_out, uint8_t *mask, int64_t *rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,12 @@
 //       device: one coalesced 16-byte-per-lane row copy per destination row, HBM-bound (reads + writes every byte
 //       once).  The slate pipeline itself can also take the permutation directly (see ltr_fused_step's callers),
 //       in which case nothing is copied at all.
+//   (3) Fixed-length slates from a ragged collection (config.json data.slate_length; the reference keeps per-query lists,
+//       utils/dataset.py:44-69): per query the first S documents or a seeded sample of S, padding behind them, the padded
+//       [B][S][F] batch, its labels, its mask and its row map in one launch (ltr_slates_build); the row map alone
+//       (ltr_slates_select) with the gather / scatter that take dense tensors to ragged order and back.
 #include "../../include/ltr_mi355x.h"
+#include "ltr_device.h"
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -29,33 +34,36 @@ namespace {
 // dst[r][:] = src[idx[r]][:], rows of `row_f4` float4s.  One workgroup handles kRowsPerBlock destination rows;
 // lanes sweep a row in 16-byte pieces (fully coalesced on both sides).  Negative indices count from the end like torch
 // indexing (idx + src_rows); an index still out of range yields a ZERO row (torch raises a device-side assert there).
+// kWrap = false (ltr_slates_gather_f32): a negative index is out of range too, and such a row is `fill`.
 constexpr int kGatherThreads = 256;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+template <bool kWrap>
 __global__ void __launch_bounds__(kGatherThreads)
 gather_rows_kernel(const f32x4 *__restrict__ src, const int64_t *__restrict__ idx, int64_t n_rows, int64_t src_rows,
-                   int row_f4, f32x4 *__restrict__ dst) {
+                   int row_f4, float fill, f32x4 *__restrict__ dst) {
     const int64_t total = n_rows * row_f4;
     for (int64_t e = (int64_t)blockIdx.x * kGatherThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kGatherThreads) {
         const int64_t r = e / row_f4;
         const int c = (int)(e - r * row_f4);
         int64_t s = idx[r];
-        if (s < 0) s += src_rows;
-        dst[e] = s >= 0 && s < src_rows ? __builtin_nontemporal_load(src + s * row_f4 + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+        if (kWrap && s < 0) s += src_rows;
+        dst[e] = s >= 0 && s < src_rows ? __builtin_nontemporal_load(src + s * row_f4 + c) : f32x4{fill, fill, fill, fill};
     }
 }
 
 // Wide rows (a whole query: 128 x 136 floats = 69 632 B): one workgroup moves a 16 KiB piece of ONE row -- the row index is read
 // once per workgroup (scalar), every lane streams 4 x 16 B with no per-element division, loads issued before the stores.
 constexpr int kGatherPiece = kGatherThreads * 4;      // float4s per workgroup
+template <bool kWrap>
 __global__ void __launch_bounds__(kGatherThreads)
 gather_rows_wide_kernel(const f32x4 *__restrict__ src, const int64_t *__restrict__ idx, int64_t n_rows, int64_t src_rows, int row_f4,
-                        int pieces, f32x4 *__restrict__ dst) {
+                        int pieces, float fill, f32x4 *__restrict__ dst) {
     for (int64_t b = blockIdx.x; b < n_rows * pieces; b += gridDim.x) {
         const int64_t r = b / pieces;
         const int piece = (int)(b - r * pieces);
         int64_t srow = idx[r];
-        if (srow < 0) srow += src_rows;
+        if (kWrap && srow < 0) srow += src_rows;
         const bool ok = srow >= 0 && srow < src_rows;
         const f32x4 *sp = src + (ok ? srow : 0) * row_f4;
         f32x4 *dp = dst + r * row_f4;
@@ -63,23 +71,205 @@ gather_rows_wide_kernel(const f32x4 *__restrict__ src, const int64_t *__restrict
         f32x4 v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (c0 + k * kGatherThreads < row_f4) v[k] = ok ? __builtin_nontemporal_load(sp + c0 + k * kGatherThreads) : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (c0 + k * kGatherThreads < row_f4) v[k] = ok ? __builtin_nontemporal_load(sp + c0 + k * kGatherThreads) : f32x4{fill, fill, fill, fill};
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (c0 + k * kGatherThreads < row_f4) __builtin_nontemporal_store(v[k], dp + c0 + k * kGatherThreads);
     }
 }
 
+template <bool kWrap>
 __global__ void __launch_bounds__(kGatherThreads)
 gather_rows_scalar_kernel(const float *__restrict__ src, const int64_t *__restrict__ idx, int64_t n_rows, int64_t src_rows,
-                          int row_f, float *__restrict__ dst) {
+                          int row_f, float fill, float *__restrict__ dst) {
     const int64_t total = n_rows * row_f;
     for (int64_t e = (int64_t)blockIdx.x * kGatherThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kGatherThreads) {
         const int64_t r = e / row_f;
         const int c = (int)(e - r * row_f);
         int64_t s = idx[r];
-        if (s < 0) s += src_rows;
-        dst[e] = s >= 0 && s < src_rows ? src[s * row_f + c] : 0.f;
+        if (kWrap && s < 0) s += src_rows;
+        dst[e] = s >= 0 && s < src_rows ? src[s * row_f + c] : fill;
+    }
+}
+
+template <bool kWrap>
+int launch_gather(const float *src, int64_t src_rows, const int64_t *idx, int64_t n_rows, int64_t row_floats, float fill, float *dst,
+                  void *stream) {
+    const bool vec = row_floats % 4 == 0 && ((uintptr_t)src & 15u) == 0 && ((uintptr_t)dst & 15u) == 0;
+    const int64_t total = vec ? n_rows * (row_floats / 4) : n_rows * row_floats;
+    int64_t blocks = (total + kGatherThreads - 1) / kGatherThreads;
+    if (blocks > 256 * 32) blocks = 256 * 32;                      // 32 workgroups per CU, grid-stride beyond
+    if (vec && row_floats / 4 >= kGatherPiece / 2) {
+        const int row_f4 = (int)(row_floats / 4), pieces = (row_f4 + kGatherPiece - 1) / kGatherPiece;
+        int64_t wg = n_rows * pieces;
+        if (wg > 256 * 64) wg = 256 * 64;
+        hipLaunchKernelGGL(gather_rows_wide_kernel<kWrap>, dim3((unsigned)wg), dim3(kGatherThreads), 0, (hipStream_t)stream,
+                           reinterpret_cast<const f32x4 *>(src), idx, n_rows, src_rows, row_f4, pieces, fill, reinterpret_cast<f32x4 *>(dst));
+    } else if (vec)
+        hipLaunchKernelGGL(gather_rows_kernel<kWrap>, dim3((unsigned)blocks), dim3(kGatherThreads), 0, (hipStream_t)stream,
+                           reinterpret_cast<const f32x4 *>(src), idx, n_rows, src_rows, (int)(row_floats / 4), fill,
+                           reinterpret_cast<f32x4 *>(dst));
+    else
+        hipLaunchKernelGGL(gather_rows_scalar_kernel<kWrap>, dim3((unsigned)blocks), dim3(kGatherThreads), 0, (hipStream_t)stream, src,
+                           idx, n_rows, src_rows, (int)row_floats, fill, dst);
+    return ltr::launch_status();
+}
+
+// dst[rows[r]][:] = src[r][:] for 0 <= rows[r] < dst_rows (T = f32x4 or float, rows of `row` T); the other dst rows are not touched.
+// The caller's rows name no destination twice, so plain stores do.
+template <class T>
+__global__ void __launch_bounds__(kGatherThreads)
+scatter_rows_kernel(const T *__restrict__ src, const int64_t *__restrict__ rows, int64_t n_slots, int row, int64_t dst_rows,
+                    T *__restrict__ dst) {
+    const int64_t total = n_slots * row;
+    for (int64_t e = (int64_t)blockIdx.x * kGatherThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kGatherThreads) {
+        const int64_t r = e / row;
+        const int c = (int)(e - r * row);
+        const int64_t d = rows[r];
+        if (d >= 0 && d < dst_rows) dst[d * row + c] = __builtin_nontemporal_load(src + e);
+    }
+}
+
+// ------------------------------------------------------------------------------------------ fixed-length slates
+// One 256-thread workgroup per listed query.  slate_select decides which k = min(len, S) documents the query keeps and in which slot
+// each sits (ascending document order); the two kernels below write the row map / mask from it, the build kernel also the rows.
+constexpr int kSlateThreads = 256;
+
+__device__ __forceinline__ uint64_t slate_key(uint64_t seed, uint64_t q, uint64_t j) {
+    uint64_t z = seed ^ (q * 0xD1B54A32D192ED03ull + j * 0x9E3779B97F4A7C15ull + 0x8CB92BA72F3D8DD7ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+struct SlatePick {
+    int64_t off;      // the query's first row
+    int k;            // real slots (0: the length is outside 1 .. LTR_MAX_SLATE)
+    bool direct;      // slot s holds local document s; otherwise slot_doc[s] (SlateLds)
+    __device__ __forceinline__ int doc(const int *slot_doc, int slot) const { return direct ? slot : slot_doc[slot]; }
+};
+
+// The workgroup's LDS.  keys: after the ranking reused as slot_doc int [S]; kept: 1 = the document's rank is below S.
+struct SlateLds {
+    uint64_t keys[LTR_MAX_SLATE];
+    uint8_t kept[LTR_MAX_SLATE];
+    int wave_tot[kSlateThreads / LTR_WAVE];
+    __device__ __forceinline__ const int *slot_doc() const { return reinterpret_cast<const int *>(keys); }
+};
+
+// Every branch around a barrier is workgroup-uniform (q, off and len are scalars).  Sampling ranks every document by counting over all
+// keys, ties by index: rank(j) = #{o : key[o] < key[j] or (key[o] == key[j] and o < j)}, kept when rank < S.  A wave ranks 64
+// CONSECUTIVE documents J0 .. J0 + 63 at a time, so the index rule is wave-uniform outside that band: before it one compare per key
+// (key[j] < key[o] is what does NOT count), behind it one compare (key[o] < key[j]), the full rule only on the band's 64 keys.  key[o] is
+// one LDS address per wave, a broadcast read.  Then each thread counts the kept flags of `chunk` consecutive documents and an exclusive
+// scan over the threads gives its first slot: kept documents fill the slots in ascending document order.
+__device__ __forceinline__ SlatePick slate_select(const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries, long long i,
+                                                  int S, int mode, uint64_t seed, SlateLds &lds) {
+    const long long q = ltr_wave_uniform(queries ? (long long)queries[i] : i);
+    SlatePick p;
+    p.off = ltr_wave_uniform(offsets[q]);
+    const int64_t len64 = ltr_wave_uniform(offsets[q + 1]) - p.off;
+    p.direct = true;
+    if (len64 < 1 || len64 > LTR_MAX_SLATE) {
+        p.k = 0;
+        return p;
+    }
+    const int len = (int)len64;
+    p.k = len < S ? len : S;
+    if (mode == LTR_SLATES_FIRST || len <= S) return p;
+    p.direct = false;
+    const int tid = threadIdx.x, lane = tid & (LTR_WAVE - 1);
+    const uint64_t *keys = lds.keys;
+    for (int j = tid; j < len; j += kSlateThreads) lds.keys[j] = slate_key(seed, (uint64_t)q, (uint64_t)j);
+    __syncthreads();
+    for (int J0 = __builtin_amdgcn_readfirstlane(tid - lane); J0 < len; J0 += kSlateThreads) {
+        const int j = J0 + lane, J1 = J0 + LTR_WAVE < len ? J0 + LTR_WAVE : len;
+        const uint64_t kj = keys[j < len ? j : len - 1];
+        int not_below = 0, below = 0;
+#pragma unroll 8
+        for (int o = 0; o < J0; ++o) not_below += kj < keys[o];
+        for (int o = J0; o < J1; ++o) below += (keys[o] < kj) | ((keys[o] == kj) & (o < j));
+#pragma unroll 8
+        for (int o = J1; o < len; ++o) below += keys[o] < kj;
+        if (j < len) lds.kept[j] = J0 - not_below + below < S;
+    }
+    __syncthreads();                                                   // flags complete, and every thread is done with the keys
+    const int chunk = (len + kSlateThreads - 1) / kSlateThreads;       // 1 .. 8 consecutive documents per thread
+    const int j0 = tid * chunk, j1 = j0 + chunk < len ? j0 + chunk : len;
+    int mine = 0;
+    for (int j = j0; j < j1; ++j) mine += lds.kept[j];
+    int incl = mine;
+    for (int o = 1; o < LTR_WAVE; o <<= 1) {
+        const int v = __shfl_up(incl, o, LTR_WAVE);
+        if (lane >= o) incl += v;
+    }
+    if (lane == LTR_WAVE - 1) lds.wave_tot[tid / LTR_WAVE] = incl;
+    __syncthreads();
+    int slot = incl - mine;
+    for (int w = 0; w < tid / LTR_WAVE; ++w) slot += lds.wave_tot[w];
+    int *slot_doc = reinterpret_cast<int *>(lds.keys);
+    for (int j = j0; j < j1; ++j)
+        if (lds.kept[j]) slot_doc[slot++] = j;                         // the ranks are a permutation: exactly S kept, slot < S
+    __syncthreads();
+    return p;
+}
+
+// rows / mask (either may be NULL) of listed query i, from the pick
+__device__ __forceinline__ void slate_write_map(const SlatePick &p, const int *slot_doc, long long i, int S, int64_t *__restrict__ rows,
+                                                uint8_t *__restrict__ mask) {
+    for (int s = threadIdx.x; s < S; s += kSlateThreads) {
+        const bool real = s < p.k;
+        if (rows) rows[i * S + s] = real ? p.off + p.doc(slot_doc, s) : -1;
+        if (mask) mask[i * S + s] = real ? 0 : 1;
+    }
+}
+
+__global__ void __launch_bounds__(kSlateThreads)
+slates_select_kernel(const int64_t *__restrict__ offsets, const int32_t *__restrict__ queries, int n_queries, int S, int mode,
+                     uint64_t seed, int64_t *__restrict__ rows, uint8_t *__restrict__ mask) {
+    __shared__ SlateLds lds;
+    const long long i = ltr_block_id();
+    if (i >= n_queries) return;
+    const SlatePick p = slate_select(offsets, queries, i, S, mode, seed, lds);
+    slate_write_map(p, lds.slot_doc(), i, S, rows, mask);
+}
+
+// The selection and the copies in one launch (T = f32x4 or float, X rows of `row` T).  The workgroup sweeps its slate's S x row
+// elements flat -- lane-contiguous on the output side, row-contiguous pieces on the input side -- four loads in flight per lane
+// before the four stores; (slot, column) advance by 256 elements without a division.
+template <class T>
+__global__ void __launch_bounds__(kSlateThreads)
+slates_build_kernel(const T *__restrict__ X, const float *__restrict__ y, const int64_t *__restrict__ offsets,
+                    const int32_t *__restrict__ queries, int n_queries, int S, unsigned row, int mode, uint64_t seed, float pad,
+                    T *__restrict__ X_out, float *__restrict__ y_out, uint8_t *__restrict__ mask, int64_t *__restrict__ rows) {
+    __shared__ SlateLds lds;
+    const long long i = ltr_block_id();
+    if (i >= n_queries) return;
+    const SlatePick p = slate_select(offsets, queries, i, S, mode, seed, lds);
+    const int *slot_doc = lds.slot_doc();
+    slate_write_map(p, slot_doc, i, S, rows, mask);
+    for (int s = threadIdx.x; s < S; s += kSlateThreads) y_out[i * S + s] = s < p.k ? y[p.off + p.doc(slot_doc, s)] : pad;
+    const T *src = X + p.off * row;
+    T *out = X_out + i * S * row;
+    const T zero = {};
+    const unsigned total = (unsigned)S * row, step_slot = kSlateThreads / row, step_col = kSlateThreads % row;   // total <= 2^31
+    unsigned slot = threadIdx.x / row, col = threadIdx.x % row;
+    for (unsigned e = threadIdx.x; e < total; e += 4 * kSlateThreads) {
+        T v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (e + u * kSlateThreads < total)
+                v[u] = (int)slot < p.k ? __builtin_nontemporal_load(src + (int64_t)p.doc(slot_doc, (int)slot) * row + col) : zero;
+            slot += step_slot;
+            col += step_col;
+            if (col >= row) {
+                col -= row;
+                ++slot;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (e + u * kSlateThreads < total) out[e + u * kSlateThreads] = v[u];
     }
 }
 
@@ -245,25 +435,60 @@ int ltr_gather_rows_f32(const float *src, int64_t src_rows, const int64_t *idx, 
     if (!src || !idx || !dst) return LTR_ERR_NULL;
     if (n_rows < 0 || src_rows < 0 || row_floats < 1 || row_floats > (1 << 28)) return LTR_ERR_SHAPE;
     if (n_rows == 0) return LTR_OK;
+    return launch_gather<true>(src, src_rows, idx, n_rows, row_floats, 0.f, dst, stream);
+}
+
+int ltr_slates_select(const int64_t *offsets, const int32_t *queries, int n_queries, int S, int mode, uint64_t seed, int64_t *rows,
+                      uint8_t *mask, void *stream) {
+    if (!offsets || !rows) return LTR_ERR_NULL;
+    if (n_queries < 0 || S < 1 || S > LTR_MAX_SLATE) return LTR_ERR_SHAPE;
+    if (mode != LTR_SLATES_FIRST && mode != LTR_SLATES_SAMPLE) return LTR_ERR_PARAM;
+    if (n_queries == 0) return LTR_OK;
+    hipLaunchKernelGGL(slates_select_kernel, ltr_grid(n_queries), dim3(kSlateThreads), 0, (hipStream_t)stream, offsets, queries,
+                       n_queries, S, mode, seed, rows, mask);
+    return ltr::launch_status();
+}
+
+int ltr_slates_gather_f32(const float *src, int64_t src_rows, const int64_t *rows, int64_t n_slots, int64_t row_floats, float fill,
+                          float *dst, void *stream) {
+    if (!src || !rows || !dst) return LTR_ERR_NULL;
+    if (n_slots < 0 || src_rows < 0 || row_floats < 1 || row_floats > (1 << 28)) return LTR_ERR_SHAPE;
+    if (n_slots == 0) return LTR_OK;
+    return launch_gather<false>(src, src_rows, rows, n_slots, row_floats, fill, dst, stream);
+}
+
+int ltr_slates_scatter_f32(const float *src, const int64_t *rows, int64_t n_slots, int64_t row_floats, int64_t dst_rows, float *dst,
+                           void *stream) {
+    if (!src || !rows || !dst) return LTR_ERR_NULL;
+    if (n_slots < 0 || dst_rows < 0 || row_floats < 1 || row_floats > (1 << 28)) return LTR_ERR_SHAPE;
+    if (n_slots == 0) return LTR_OK;
     const bool vec = row_floats % 4 == 0 && ((uintptr_t)src & 15u) == 0 && ((uintptr_t)dst & 15u) == 0;
-    const int64_t total = vec ? n_rows * (row_floats / 4) : n_rows * row_floats;
-    int64_t blocks = (total + kGatherThreads - 1) / kGatherThreads;
-    if (blocks > 256 * 32) blocks = 256 * 32;                      // 32 workgroups per CU, grid-stride beyond
-    if (vec && row_floats / 4 >= kGatherPiece / 2) {
-        const int row_f4 = (int)(row_floats / 4), pieces = (row_f4 + kGatherPiece - 1) / kGatherPiece;
-        int64_t wg = n_rows * pieces;
-        if (wg > 256 * 64) wg = 256 * 64;
-        hipLaunchKernelGGL(gather_rows_wide_kernel, dim3((unsigned)wg), dim3(kGatherThreads), 0, (hipStream_t)stream,
-                           reinterpret_cast<const f32x4 *>(src), idx, n_rows, src_rows, row_f4, pieces, reinterpret_cast<f32x4 *>(dst));
-    } else if (vec)
-        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)blocks), dim3(kGatherThreads), 0, (hipStream_t)stream,
-                           reinterpret_cast<const f32x4 *>(src), idx, n_rows, src_rows, (int)(row_floats / 4),
-                           reinterpret_cast<f32x4 *>(dst));
+    const int row = (int)(vec ? row_floats / 4 : row_floats);
+    int64_t blocks = (n_slots * row + kGatherThreads - 1) / kGatherThreads;
+    if (blocks > 256 * 32) blocks = 256 * 32;                      // grid-stride beyond, as the gather
+    if (vec)
+        hipLaunchKernelGGL(scatter_rows_kernel<f32x4>, dim3((unsigned)blocks), dim3(kGatherThreads), 0, (hipStream_t)stream,
+                           reinterpret_cast<const f32x4 *>(src), rows, n_slots, row, dst_rows, reinterpret_cast<f32x4 *>(dst));
     else
-        hipLaunchKernelGGL(gather_rows_scalar_kernel, dim3((unsigned)blocks), dim3(kGatherThreads), 0, (hipStream_t)stream, src,
-                           idx, n_rows, src_rows, (int)row_floats, dst);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? LTR_OK : (int)e;
+        hipLaunchKernelGGL(scatter_rows_kernel<float>, dim3((unsigned)blocks), dim3(kGatherThreads), 0, (hipStream_t)stream, src, rows,
+                           n_slots, row, dst_rows, dst);
+    return ltr::launch_status();
+}
+
+int ltr_slates_build(const float *X, const float *y, const int64_t *offsets, const int32_t *queries, int n_queries, int S, int F,
+                     int mode, uint64_t seed, float pad, float *X_out, float *y_out, uint8_t *mask, int64_t *rows, void *stream) {
+    if (!X || !y || !offsets || !X_out || !y_out) return LTR_ERR_NULL;
+    if (n_queries < 0 || S < 1 || S > LTR_MAX_SLATE || F < 1 || F > (1 << 20)) return LTR_ERR_SHAPE;
+    if (mode != LTR_SLATES_FIRST && mode != LTR_SLATES_SAMPLE) return LTR_ERR_PARAM;
+    if (n_queries == 0) return LTR_OK;
+    if (F % 4 == 0 && ((uintptr_t)X & 15u) == 0 && ((uintptr_t)X_out & 15u) == 0)
+        hipLaunchKernelGGL(slates_build_kernel<f32x4>, ltr_grid(n_queries), dim3(kSlateThreads), 0, (hipStream_t)stream,
+                           reinterpret_cast<const f32x4 *>(X), y, offsets, queries, n_queries, S, (unsigned)(F / 4), mode, seed, pad,
+                           reinterpret_cast<f32x4 *>(X_out), y_out, mask, rows);
+    else
+        hipLaunchKernelGGL(slates_build_kernel<float>, ltr_grid(n_queries), dim3(kSlateThreads), 0, (hipStream_t)stream, X, y, offsets,
+                           queries, n_queries, S, (unsigned)F, mode, seed, pad, X_out, y_out, mask, rows);
+    return ltr::launch_status();
 }
 
 int ltr_svmlight_scan(const char *path, int64_t *n_docs, int32_t *min_feature_id, int32_t *max_feature_id, int n_threads) {

@@ -71,6 +71,11 @@ _PROTOTYPES = {
     "ltr_svmlight_scan": (c_int, [c_char_p, P, P, P, c_int]),
     "ltr_svmlight_load": (c_int, [c_char_p, c_int64, c_int, c_int, P, P, P, c_int]),
     "ltr_gather_rows_f32": (c_int, [P, c_int64, P, c_int64, c_int64, P, P]),
+    # fixed-length slates from a ragged collection (ltr_mi355x.slates)
+    "ltr_slates_select": (c_int, [P, P, c_int, c_int, c_int, c_uint64, P, P, P]),
+    "ltr_slates_gather_f32": (c_int, [P, c_int64, P, c_int64, c_int64, c_float, P, P]),
+    "ltr_slates_scatter_f32": (c_int, [P, P, c_int64, c_int64, c_int64, P, P]),
+    "ltr_slates_build": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_uint64, c_float, P, P, P, P, P]),
     # include/ltr_encoder.h (row f-3)
     "ltr_enc_cast_bf16": (c_int, [P, P, c_int64, P]),
     "ltr_enc_splitk_epilogue": (c_int, [P, c_int, c_int64, c_int, P, c_float, c_uint64, c_int, P, P, P]),

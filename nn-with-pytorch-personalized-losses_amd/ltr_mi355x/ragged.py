@@ -148,6 +148,11 @@ class RaggedSlates:
             order = (torch.cat(parts) - q0) if parts else self.order[:0]
         return RaggedSlates._made(off_h, order_h, np.asarray(start, dtype=np.int64), self.device, offsets, order)
 
+    def fixed_length(self, S, mode="first", seed=0):
+        """The fixed-length view of these queries (config.json data.slate_length): ltr_mi355x.slates.fixed_length(self, ...)."""
+        from .slates import fixed_length
+        return fixed_length(self, S, mode=mode, seed=seed)
+
     def permuted(self, perm):
         """Queries in the order `perm` (a permutation of 0 .. Q - 1, host array or tensor): returns (new_slates, doc_index) where
         doc_index [n_docs] int64 (on the slates' device when they have one) lists the old document rows in their new order --
