@@ -470,6 +470,84 @@ int ltr_linear_risk_combine(const float *R, const float *dmat, int dmat_stride, 
 int ltr_linear_grid(int n_cus);
 
 /* =====================================================================================================
+ * FC scorers with 137 .. 1024 input features (csrc/ltr_wide.hip): the public LETOR collections beyond the reference's two
+ * (Istella 220, Yahoo LTRC 700).  The slate pipeline above holds a 128-document tile of at most 136 features in LDS; these widths
+ * run as a chain of launches on one exact-fp32 GEMM.  No LTR_F16X2 form: both libraries compile the same code.
+ *
+ * ---- ltr_gemm_f32: the exact-fp32 sibling of ltr_enc_gemm_bf16 (ltr_encoder.h), on v_mfma_f32_16x16x4_f32 -- every output is
+ * a k-ordered fp32 fmaf chain.       C[m][n] = sum_k A(m,k) * B(n,k)        m < M, n < N, k < K
+ *   A(m,k) = a_kmajor ? A[k*lda + m] : A[m*lda + k]   (same for B); no operand is ever transposed in memory:
+ *        forward   z = x W^T      A = x [T][K],  B = W [N][K]                   (0, 0)      doubleLayer.py:62-66, tripleLayer.py:14-16
+ *        d h       = dz W         A = dz [T][N], B = W [N][K] k-major           (0, 1)
+ *        d W       = dz^T x       A = dz [T][N] k-major, B = x [T][K] k-major   (1, 1), split over T
+ *   64 x 64 output tile per 256-thread workgroup, 16-wide k tiles staged through LDS.  M >= 0 and K >= 1 of any size (64-bit
+ *   indices), 1 <= N <= 1024, odd extents included.  An operand is read 16 bytes per lane when its base is 16-byte aligned and its
+ *   leading dimension a multiple of 4, else 4 bytes per lane; rows and k outside the extents are zero-filled in LDS, never read.
+ *   Epilogue, in this order (all optional): + bias[n]; act (LTR_GEMM_ACT_*; the sigmoid is the correctly rounded 1 / (1 + exp(-v)));
+ *   gate through the saved post-activation tensor g = gate[m*ldg + n] -- LTR_GEMM_GATE_RELU: v = g > 0 ? v * gate_scale : 0 (the
+ *   ReLU + dropout backward), LTR_GEMM_GATE_SIGMOID: v * (g * (1 - g)); dropout with the SCORERS' keep stream: `dropout` is the
+ *   drop code of the entries above (0, 1 or 1 | bits of p), unit (doc = m, n) of layer `drop_layer` is kept exactly where
+ *   ltr_dropout_keep_mask / ltr_dropout_keep_mask_p (seed, drop_layer) say so, or where keep[m*N + n] != 0 when `keep` is given
+ *   (bytes; used INSTEAD of the stream); kept values are multiplied by the fp32 value 1 / (1 - p); store fp32 (ldc).
+ *   splits > 1: a split over K in slices of ceil(ceil(K / 16) / splits) * 16; slice z writes its raw partial to C + z*M*ldc (no
+ *   epilogue), a slice past the end of K writes zeros -- reduce with ltr_enc_sum_partials.  No atomics: same inputs, same bits.
+ *   NULL A / B / C (or a gate kind without gate): LTR_ERR_NULL; extents or leading dimensions out of range, splits outside
+ *   1 .. 1024: LTR_ERR_SHAPE; unknown act / gate kind, drop_layer outside 0 .. 1, p outside (0, 1): LTR_ERR_PARAM; a pointer not
+ *   4-byte aligned: LTR_ERR_ALIGN; M == 0: LTR_OK without a launch. */
+enum { LTR_GEMM_ACT_NONE = 0, LTR_GEMM_ACT_RELU = 1, LTR_GEMM_ACT_SIGMOID = 2 };
+enum { LTR_GEMM_GATE_NONE = 0, LTR_GEMM_GATE_RELU = 1, LTR_GEMM_GATE_SIGMOID = 2 };
+typedef struct ltr_gemm_f32_desc {
+    const float *A, *B;
+    int64_t M, N, K, lda, ldb, ldc;
+    int32_t a_kmajor, b_kmajor, splits, act;
+    float *C;
+    const float *bias;
+    const float *gate;
+    int64_t ldg;
+    int32_t gate_kind;
+    float gate_scale;
+    int32_t dropout, drop_layer;
+    uint64_t seed;
+    const uint8_t *keep;
+} ltr_gemm_f32_desc;
+int ltr_gemm_f32(const ltr_gemm_f32_desc *desc /* host pointer */, void *stream);
+
+/* Column sums of an fp32 [T][N] tensor (leading dimension ld), the bias gradients: partials[blk][n] = sum over workgroup blk's
+ * contiguous row range (ceil(T / nblk) rows each, fixed order) of row_weights[t] * y[t*ld + n]; row_weights == NULL: 1 (non-NULL:
+ * d w3 = sum_d ds_d h_d).  Reduce with ltr_enc_sum_partials(partials, nblk, N, ...).  1 <= N <= 1024, ld >= N, 1 <= nblk <= 65535. */
+int ltr_colsum_f32(const float *y, int64_t T, int N, int64_t ld, const float *row_weights, float *partials, int nblk, void *stream);
+
+/* ---- The training chain as two launchers, the wide counterparts of ltr_mlp_forward_save / ltr_mlp_backward_saved.  They enqueue
+ * several kernels on `stream`, allocate nothing and never synchronise (capturable).
+ *   LTR_WIDE_RELU3     F -> H1 -> H2 -> 1, ReLU + dropout after fc1 and fc2: DoubleLayerNet (doubleLayer.py:54-73; H1 = H2 = F there)
+ *   LTR_WIDE_SIGMOID2  F -> H1 -> 1, sigmoid: TripleLayerNet (tripleLayer.py:5-17) folded by ltr_triple_fold with copies = 1
+ *                      (H1 = 32); H2 is ignored
+ * `params`: HOST array of device pointers W1 [H1][F], b1, [W2 [H2][H1], b2,] w3, b3 as the module holds them.  keep1 / keep2:
+ * optional explicit keep masks [n_docs][H1] / [n_docs][H2], else the stream of (seed, layer 0 / 1).
+ * acts (ltr_wide_acts_floats): the saved post-activation layers, row-major, dropout applied: h1 [n_docs][H1] at 0 and, for RELU3,
+ *   h2 [n_docs][H2] at r4(n_docs H1), r4(x) = x rounded up to a multiple of 4;  floats = r4(n_docs H1) [+ r4(n_docs H2)].
+ * ws (ltr_wide_ws_floats): RELU3: dz2 [n_docs][H2] | dz1 [n_docs][H1] | partials; SIGMOID2: dz1 | partials.
+ *   floats = [r4(n_docs H2) +] r4(n_docs H1) + r4(max(grid max(H1, H2), splits(H1, F) H1 F [, splits(H2, H1) H2 H1])),
+ *   splits(M, N) = clamp(ceil(grid / (ceil(M / 64) ceil(N / 64))), 1, min(ceil(max(n_docs, 1) / 64), 1024)): the slices of that
+ *   weight-gradient GEMM; `grid` (1 .. 65535) is the number of workgroups a launch should fill.
+ * Forward: h1 = drop(relu(X W1^T + b1)), h2 = drop(relu(h1 W2^T + b2)), scores = h2 . w3 + b3 (one wave per document).
+ * Backward (reads the saved layers, never the dropout stream; `dropout` only selects the slope 1 / (1 - p); no dL/dX):
+ *   dw3 = sum_d ds_d h2_d, db3 = sum_d ds_d; dz2 = (ds (x) w3) gated by h2; dW2 = dz2^T h1 (split over documents), db2 = colsum dz2;
+ *   dz1 = (dz2 W2) gated by h1; dW1 = dz1^T X, db1 = colsum dz1.  flat_grad: RELU3 [W1 | b1 | W2 | b2 | w3 | b3] in parameters()
+ *   order; SIGMOID2 [dW1e H1 x F | db1e H1 | dw3e H1 | db3], the g2 layout ltr_triple_unfold_grads takes.
+ * Checked in this order before any launch: NULL required pointer (X, params and its entries, scores / dscores, acts, ws,
+ * flat_grad): LTR_ERR_NULL; F, H1 (RELU3: H2) outside 1 .. 1024, n_docs < 0, grid outside 1 .. 65535: LTR_ERR_SHAPE; unknown kind,
+ * a drop code with p outside (0, 1): LTR_ERR_PARAM; X, acts or ws not 16-byte aligned: LTR_ERR_ALIGN; n_docs == 0: LTR_OK
+ * without a launch (the backward zeroes flat_grad with a memset on the stream). */
+enum { LTR_WIDE_RELU3 = 0, LTR_WIDE_SIGMOID2 = 1 };
+int64_t ltr_wide_acts_floats(int kind, int F, int H1, int H2, int64_t n_docs);            /* < 0: LTR_ERR_* */
+int64_t ltr_wide_ws_floats(int kind, int F, int H1, int H2, int64_t n_docs, int grid);    /* < 0: LTR_ERR_* */
+int ltr_wide_forward_save(int kind, int F, int H1, int H2, const float *X, int64_t n_docs, const float *const *params, int dropout,
+                          uint64_t seed, const uint8_t *keep1, const uint8_t *keep2, float *scores, float *acts, void *stream);
+int ltr_wide_backward_saved(int kind, int F, int H1, int H2, const float *X, int64_t n_docs, const float *const *params, int dropout,
+                            const float *acts, const float *dscores, float *ws, int grid, float *flat_grad, void *stream);
+
+/* =====================================================================================================
  * Data path in front of the pipeline.
  *
  * ---- get_data(info_dataset, type_file)                                        utils/dataset.py:33-69

@@ -138,6 +138,26 @@ __device__ __forceinline__ float row_reduce(const SlateGroup &g, float v) {
     return v;
 }
 
+// The scorers' counter-based dropout keep stream (ltr_scorer.hip, ltr_fcw.h, ltr_wide.hip; exported by ltr_dropout_keep_mask[_p]).
+__device__ __forceinline__ unsigned mix32(unsigned h) {
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+
+// 32 keep bits for features [32*word, 32*word+32) of document `doc` in dropout layer `layer`.  The first two mixing steps
+// depend on (seed, layer, doc) only: keep_prefix() is that part, shared by every word of a document (activate below).
+__device__ __forceinline__ unsigned keep_prefix(unsigned long long seed, int layer, long long doc) {
+    unsigned h = (unsigned)seed ^ (0x9E3779B9u * (unsigned)(layer + 1));
+    h = mix32(h ^ (unsigned)doc);
+    return mix32(h ^ (unsigned)((unsigned long long)doc >> 32) ^ (unsigned)(seed >> 32));
+}
+__device__ __forceinline__ unsigned keep_word_at(unsigned prefix, int word) {
+    return mix32(prefix + 0x27D4EB2Fu * (unsigned)(word + 1));
+}
+__device__ __forceinline__ unsigned keep_word(unsigned long long seed, int layer, long long doc, int word) {
+    return keep_word_at(keep_prefix(seed, layer, doc), word);
+}
+
 __host__ __device__ inline int next_pow2(int v) {
     int p = 1;
     while (p < v) p <<= 1;

@@ -195,25 +195,6 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-__device__ __forceinline__ unsigned mix32(unsigned h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-
-// 32 keep bits for features [32*word, 32*word+32) of document `doc` in dropout layer `layer`.  The first two mixing steps
-// depend on (seed, layer, doc) only: keep_prefix() is that part, shared by every word of a document (activate below).
-__device__ __forceinline__ unsigned keep_prefix(unsigned long long seed, int layer, long long doc) {
-    unsigned h = (unsigned)seed ^ (0x9E3779B9u * (unsigned)(layer + 1));
-    h = mix32(h ^ (unsigned)doc);
-    return mix32(h ^ (unsigned)((unsigned long long)doc >> 32) ^ (unsigned)(seed >> 32));
-}
-__device__ __forceinline__ unsigned keep_word_at(unsigned prefix, int word) {
-    return mix32(prefix + 0x27D4EB2Fu * (unsigned)(word + 1));
-}
-__device__ __forceinline__ unsigned keep_word(unsigned long long seed, int layer, long long doc, int word) {
-    return keep_word_at(keep_prefix(seed, layer, doc), word);
-}
-
 // Sum over the 16 lanes of a DPP row (= the 16 documents sharing one q) for FOUR values at once; the totals land in lane 15 of the
 // row.  Every step is ONE v_add_f32_dpp: written with __builtin_amdgcn_update_dpp, hipcc fuses only the row_shr:2 / :4 steps and
 // expands the other two into copy + v_mov_b32_dpp + v_add_f32 (two extra instructions per step and value, in kernels whose non-matrix

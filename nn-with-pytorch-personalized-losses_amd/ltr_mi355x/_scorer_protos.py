@@ -35,6 +35,13 @@ PROTOTYPES = {
     "ltr_linear_risk_rows": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, c_int, P]),
     "ltr_linear_risk_combine": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P]),
     "ltr_linear_grid": (c_int, [c_int]),
+    # FC scorers with 137 .. 1024 input features (csrc/ltr_wide.hip)
+    "ltr_gemm_f32": (c_int, [P, P]),
+    "ltr_colsum_f32": (c_int, [P, c_int64, c_int, c_int64, P, P, c_int, P]),
+    "ltr_wide_acts_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int64]),
+    "ltr_wide_ws_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int64, c_int]),
+    "ltr_wide_forward_save": (c_int, [c_int, c_int, c_int, c_int, P, c_int64, P, c_int, c_uint64, P, P, P, P, P]),
+    "ltr_wide_backward_saved": (c_int, [c_int, c_int, c_int, c_int, P, c_int64, P, c_int, P, P, P, c_int, P, P]),
 }
 
 

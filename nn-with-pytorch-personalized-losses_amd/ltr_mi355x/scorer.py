@@ -353,8 +353,9 @@ class FusedRanker:
         self._init_risk(loss, risk_args)
         self.module = module
         if module._ltr_net == NET_WIDE:
-            raise NotImplementedError("the fused step is built for scorers of up to 136 input features; wider networks run as "
-                                      "net(x, None, None) + the loss + backward() (ltr_mi355x.scorer.wide_forward)")
+            raise NotImplementedError("the fused step of this class is built for scorers of up to 136 input features; wider networks "
+                                      "(137 .. 1024) train through ltr_mi355x.wide.WideFusedRanker, or as net(x, None, None) + the "
+                                      "loss + backward() (ltr_mi355x.scorer.wide_forward)")
         self.info = NetInfo.get(module._ltr_net)
         self.net = self.info.net           # the compiled network id the kernels run
         self._init_loss(loss, alpha, eps, padded_value_indicator, apply_sigmoid, weighing_scheme, k, sigma, mu, reduction, reduction_log)
